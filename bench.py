@@ -214,6 +214,11 @@ def secondary_legs(spec, gpus=1, layers=0):
     return legs
 
 
+def secondary_multi_spec(spec, world):
+    """--secondary-multi as given; by default BASELINE config 4 ("13b:4": Llama-2-13B, bs=32 batch-sharded) at --gpus 8, none otherwise"""
+    return spec if spec is not None else ('13b:4' if world == 8 else '')
+
+
 def compact_leg(j, name, wall_s=None):
     """One secondary leg as ~300 bytes: what a reader of the driver's captured tail needs to judge the leg; the prose that is the same for
     every leg lives once in the headline's `notes` table, the leg's full record in its own BENCH_DETAIL line / detail file."""
@@ -279,6 +284,55 @@ def compact_record(out):
         comp['secondary'] = out['secondary']
     comp['notes'] = NOTES
     return comp
+
+
+DUMP_LOGITS_BYTES = 48 << 20     # --dump-outputs: the logits' share of the 64 MB a dump may take (the token arrays are a few KB)
+
+
+def last_step_logit_rows(Ts, wide):
+    """--dump-outputs: where the last verify step left the logits of each tree row.  Ts = tree sizes of this rank's sequences in the
+    last step (sequence order).  -> [(sequence, tree row, row of the logits buffer)] for the rows the buffer still holds.  One sequence:
+    eng.logits(), or eng.mlogits() for a wide tree, row = tree row.  A batch: eng.mlogits(), row = 64 x block + tree row, holding the
+    LAST pass of the step only (more than 8 sequences run as passes of 8 blocks); a wide tree takes ceil(T / 64) consecutive blocks."""
+    if len(Ts) == 1:
+        return [(0, r, r) for r in range(Ts[0])]
+    out = []
+    if wide:
+        b0 = 0
+        for i, T in enumerate(Ts):
+            out += [(i, r, 64 * b0 + r) for r in range(T)]
+            b0 += (T + 63) // 64
+        return out
+    g0 = 8 * ((len(Ts) - 1) // 8)
+    for i in range(g0, len(Ts)):
+        out += [(i, r, 64 * (i - g0) + r) for r in range(Ts[i])]
+    return out
+
+
+def dump_outputs(path, eng, seqs, prompt_len, Ts, n_acc, wide, rank=0, world=1):
+    """--dump-outputs DIR, called after the timed steps: what the timed path computed, as float64 / float32 .npy files (a rank of an
+    N > 1 job adds _rank<r> to the names).  generated_tokens [B][n] = every token emitted after the prompt so far, last_step_tokens
+    [B][n] = the tokens the last step accepted (both -1 padded), last_step_logits [rows][vocab] = that step's logits of the rows in
+    last_step_logit_rows [rows][2] = (sequence, tree row) — a fixed, seeded sample of the rows where all of them exceed the budget."""
+    def padded(lists):
+        a = np.full((len(lists), max(len(x) for x in lists)), -1.0)
+        for i, x in enumerate(lists):
+            a[i, :len(x)] = x
+        return a
+    rows = last_step_logit_rows(Ts, wide)
+    buf = eng.logits() if len(Ts) == 1 and not wide else eng.mlogits()
+    cap = max(1, DUMP_LOGITS_BYTES // world // (4 * buf.shape[1]))
+    if len(rows) > cap:
+        keep = np.sort(np.random.RandomState(0).choice(len(rows), cap, replace=False))
+        rows = [rows[k] for k in keep]
+    idx = torch.tensor([r[2] for r in rows], dtype=torch.long, device=buf.device)
+    arrays = {'generated_tokens': padded([s[prompt_len:] for s in seqs]),
+              'last_step_tokens': padded([s[len(s) - n:] for s, n in zip(seqs, n_acc)]),
+              'last_step_logits': buf.index_select(0, idx).float().cpu().numpy(),
+              'last_step_logit_rows': np.array([r[:2] for r in rows], dtype=np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ('' if world == 1 else '_rank%d' % rank) + '.npy'), a)
 
 
 def cpu_baseline_leg(shape, sd_cpu, prompt, copies, branch_length, decoding_length, verify_steps=5, threads=None):
@@ -426,6 +480,9 @@ def main():
     ap.add_argument('--cpu-baseline-only', action='store_true',
                     help='no GPU: time only the cpu_baseline leg (the reference itself where /root/reference is importable, else the port) on the '
                          'same model shape / prompt / trie warm-up rule and print it — how the "reference" kind is measured in the build container')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed steps, write what they computed (emitted tokens; the last step\'s accepted tokens and logits) as '
+                         'DIR/<name>.npy, at most 64 MB: the inputs are seeded, so two builds can be compared output for output (dump_outputs)')
     args = ap.parse_args()
     if args.cpu_baseline_only:
         return cpu_only(args)
@@ -740,6 +797,8 @@ def main():
     correct = all(seqs[i][P:P + len(truths[gidx[i]])] == truths[gidx[i]][:len(seqs[i]) - P] for i in range(B))
     ctx_timed = float(np.mean(ctxs[c0:c0 + K]))      # mean context of the TIMED steps (the legs below keep extending the sequence)
     ctx_end_timed = eng.n_keys if B == 1 else int(np.mean(eng.slot_keys[:B]))
+    if args.dump_outputs:                # before the legs below run more steps on the engine
+        dump_outputs(args.dump_outputs, eng, seqs, P, dls[-B:], edls[-B:], wide, rank, world)
     native = None
     if B == 1 and not wide and not dist_on and len(seqs[0]) + (BL + 1) * (16 + 24) < max_length - 2 * DL:
         # informational: the same steps through the native loop (la_lookahead_decode, what lookahead_generation() uses when
@@ -888,7 +947,7 @@ def main():
     sec_ok = (not args.layers) or args.secondary_layers > 0
     if world == 1 and B == 1 and args.model == '7b' and sec_ok and args.secondary and not os.environ.get('BENCH_IS_SECONDARY'):
         secondary = secondary_legs(args.secondary, layers=args.secondary_layers)
-    multi = args.secondary_multi if args.secondary_multi is not None else ('13b:4' if world == 8 else '')
+    multi = secondary_multi_spec(args.secondary_multi, world)
     if world > 1 and B == 1 and args.model == '7b' and sec_ok and multi and not os.environ.get('BENCH_IS_SECONDARY'):
         # BASELINE config 4 (and any other listed leg) as its own N-rank job on the same GPUs: the other ranks of this job have
         # left the group and are exiting; 288 GB per GPU hold both models, so nothing has to be freed first

@@ -97,6 +97,57 @@ def test_self_launch_command_and_clean_environment(monkeypatch):
     assert 1024 < p < 65536
 
 
+def test_eight_rank_run_adds_config4_as_its_own_job_by_default():
+    """`python bench.py --gpus 8` (the driver's scaling run) follows the headline with BASELINE config 4 — Llama-2-13B, 4 sequences per
+    GPU = bs 32 over the 8 ranks — as its own 8-rank job; other rank counts add none unless --secondary-multi names legs."""
+    assert bench.secondary_multi_spec(None, 8) == '13b:4'
+    assert bench.secondary_multi_spec(None, 2) == '' and bench.secondary_multi_spec(None, 4) == ''
+    assert bench.secondary_multi_spec('13b:4', 2) == '13b:4' and bench.secondary_multi_spec('', 8) == ''
+
+
+def test_dump_maps_every_tree_row_of_the_last_step_to_its_logits_row():
+    """--dump-outputs: one sequence reads its tree rows in order; a batch reads block b = sequence b of the last pass (8 blocks per
+    pass: with 10 sequences only the second pass, sequences 8 and 9, is still in the buffer); wide trees take ceil(T / 64) blocks."""
+    assert bench.last_step_logit_rows([5], False) == [(0, r, r) for r in range(5)]
+    assert bench.last_step_logit_rows([70], True) == [(0, r, r) for r in range(70)]
+    got = bench.last_step_logit_rows([3, 1, 64], False)
+    assert got == [(0, 0, 0), (0, 1, 1), (0, 2, 2), (1, 0, 64)] + [(2, r, 128 + r) for r in range(64)]
+    got = bench.last_step_logit_rows([4] * 8 + [2, 3], False)
+    assert got == [(8, 0, 0), (8, 1, 1), (9, 0, 64), (9, 1, 65), (9, 2, 66)]
+    got = bench.last_step_logit_rows([65, 2], True)
+    assert got == [(0, r, r) for r in range(65)] + [(1, 0, 128), (1, 1, 129)]
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_rows_beyond_the_budget(tmp_path, monkeypatch):
+    """dump_outputs on a stand-in engine (CPU logits buffers): float64 tokens padded with -1, float32 logits of the mapped rows, and past
+    the byte budget a fixed, seeded sample of the rows (the same rows on every call)."""
+    import torch
+
+    class Eng(object):
+        buf = torch.randn(8 * 64, 50, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+
+        def logits(self):
+            return self.buf[:64]
+
+        def mlogits(self):
+            return self.buf
+    seqs = [[7, 7, 7, 11, 12, 13], [7, 7, 7, 21]]
+    bench.dump_outputs(str(tmp_path / 'all'), Eng(), seqs, 3, [3, 2], [2, 1], False)
+    d = {n: np.load(str(tmp_path / 'all' / (n + '.npy'))) for n in ('generated_tokens', 'last_step_tokens', 'last_step_logits', 'last_step_logit_rows')}
+    assert d['generated_tokens'].dtype == np.float64 and d['generated_tokens'].tolist() == [[11, 12, 13], [21, -1, -1]]
+    assert d['last_step_tokens'].tolist() == [[12, 13], [21, -1]]
+    assert d['last_step_logit_rows'].tolist() == [[0, 0], [0, 1], [0, 2], [1, 0], [1, 1]]
+    assert d['last_step_logits'].dtype == np.float32
+    assert np.array_equal(d['last_step_logits'], Eng.buf[[0, 1, 2, 64, 65]].float().numpy())
+    monkeypatch.setattr(bench, 'DUMP_LOGITS_BYTES', 3 * 4 * 50)          # room for 3 of the 5 rows
+    for sub in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / sub), Eng(), seqs, 3, [3, 2], [2, 1], False)
+    rows = np.load(str(tmp_path / 's1' / 'last_step_logit_rows.npy'))
+    assert rows.shape == (3, 2) and np.array_equal(rows, np.load(str(tmp_path / 's2' / 'last_step_logit_rows.npy')))
+    buf_rows = [64 * int(s) + int(r) for s, r in rows]
+    assert np.array_equal(np.load(str(tmp_path / 's1' / 'last_step_logits.npy')), Eng.buf[buf_rows].float().numpy())
+
+
 def test_self_launch_runs_two_gloo_ranks_end_to_end(tmp_path):
     """The self-launch path itself, on CPU: a stub 'bench' with the same launcher spawns 2 ranks through torch.distributed.run,
     they form a gloo group on 127.0.0.1 and rank 0 prints ONE line."""
@@ -160,31 +211,19 @@ def test_host_batch_drafts_equals_per_sample_queries():
     assert bench.host_batch_drafts(cache, [[V + 5, V + 6]], [10], 64, 12, [12])[0][0].tolist() == [V + 6]
 
 
-def test_cpu_baseline_reference_leg_equals_the_port_when_the_reference_is_importable():
+def test_cpu_baseline_reference_leg_equals_the_port():
     """`cpu_baseline.kind = "reference"` (oracle/reference_cpu.py): the reference's own lookahead_generation + LookaheadCache + LlamaForCausalLM,
     imported in place, must emit the tokens and the per-step draft / accept lengths of the port (oracle loop) on the same model, prompt and trie warm-up —
-    the two legs are interchangeable as the reported baseline.  Skipped where /root/reference is absent (the GPU box)."""
-    import pytest
-    import torch
-    from oracle import reference_cpu
-    if not reference_cpu.reference_available():
-        pytest.skip('/root/reference not present')
+    the two legs are interchangeable as the reported baseline.  The reference leg is the one recorded by oracle/gen_golden_cpu_leg.py
+    (tests/golden/cpu_baseline_reference_leg.json) on the inputs built here."""
     from oracle import llama_oracle as lo
+    from oracle.gen_golden_cpu_leg import OUT, leg_inputs
     from oracle.trie_oracle import TrieOracle
-    from tests.tiny_model import tiny_decisive_weights, tiny_shape
-    s = tiny_shape()
-    sd = tiny_decisive_weights(0, torch.float32)
-    prompt = bench.phrase_prompt(7, 40, s.vocab)
+    s, sd, prompt, seq, copies = leg_inputs()
+    with open(OUT) as f:
+        ref = json.load(f)
+    assert ref['kind'] == 'reference' and ref['verify_steps'] == 4 and ref['cores'] == 2 and ref['dtype'] == 'float32'
     model = lo.OracleLlama(s, sd)
-    seq = list(prompt)
-    lg, past = model.forward(torch.tensor(seq), torch.tril(torch.ones((40, 40), dtype=torch.long)), None)
-    for _ in range(60):
-        t = int(lg[-1].float().argmax())
-        seq.append(t)
-        lg, past = model.forward(torch.tensor([t]), torch.ones((1, len(seq)), dtype=torch.long), past)
-    copies = bench.noisy_copies(prompt[-2:] + seq[40:], 6, 0.3, s.vocab, seed=99)
-    ref = reference_cpu.reference_lookahead_loop(s, sd, prompt, copies, 12, 64, verify_steps=4, threads=2, dtype=torch.float32)
-    assert ref['kind'] == 'reference' and ref['verify_steps'] == 4 and ref['value'] > 0 and ref['cores'] == 2
     cache = TrieOracle(eos_ids=[None])
     for c in copies:
         cache.put(c, branch_length=13, mode='output', idx=-1)

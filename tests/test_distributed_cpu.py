@@ -20,6 +20,12 @@ def _free_port():
     return p
 
 
+def _rendezvous():
+    """The workers' barrier before leaving the group.  dist.barrier() asks torch for the accelerator, which starts the GPU runtime in
+    every rank on a machine with a GPU; an all-reduce of a host tensor is the same rendezvous over gloo and leaves the device alone."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _streams(world, steps):
     rng = random.Random(3)
     phrases = [[rng.randrange(3, 60) for _ in range(rng.randint(3, 9))] for _ in range(10)]
@@ -73,7 +79,7 @@ def _worker(rank, world, port, steps, q):
         ids, mask, sizes = cache.hier_get(qy, decoding_length=64, branch_length=12, min_output_size=32, mode='mix', idx=rank)
         res.append((ids, mask.tolist(), sizes))
     q.put((rank, seen, res, cache.stats()))
-    dist.barrier()
+    _rendezvous()
     dist.destroy_process_group()
 
 
@@ -155,7 +161,7 @@ def _worker_native_fails(rank, world, port, q):
         g._init_native_agreed(strict=False)
     out = g.gather([10 + rank, 20 + rank])
     q.put((rank, g._comm is None, len(w) == 1, out))
-    dist.barrier()
+    _rendezvous()
     dist.destroy_process_group()
 
 
@@ -253,7 +259,7 @@ def _worker_sharded(rank, world, port, b_loc, mode, q):
                                  return_dict_in_generate=True, decoding_kwargs=dk)
     q.put((rank, out.sequences.cpu().numpy().tolist(), out.kwargs['edls'], record, _queries(m.lookahead_cache, world * b_loc, shape.vocab),
            m.lookahead_cache.stats()))
-    dist.barrier()
+    _rendezvous()
     dist.destroy_process_group()
 
 
@@ -355,7 +361,7 @@ def _worker_sharded_failure(rank, world, port, b_loc, mode, q):
                                   return_dict_in_generate=True, decoding_kwargs=dict(dk))
     q.put((rank, err, seqs, out2.sequences.cpu().numpy().tolist(), (failed_seen, list(g.failed_ranks)), _queries(m.lookahead_cache, world * b_loc, shape.vocab),
            m.lookahead_cache.stats()))
-    dist.barrier()
+    _rendezvous()
     dist.destroy_process_group()
 
 
