@@ -43,7 +43,7 @@ extern "C" {
 #define LA_MOE_MAX_E      8   /* experts per mixture-of-experts layer (Mixtral: 8, top-2) */
 
 /* ABI version: bumped when a signature changes. */
-#define LA_ABI_VERSION  12   /* bumped whenever a struct layout or an entry point changes */
+#define LA_ABI_VERSION  13   /* bumped whenever a struct layout or an entry point changes */
 int          la_abi_version(void);   /* == LA_ABI_VERSION of the header the library was built from */
 /* Storage / MFMA-input type of the loaded library: 0 = bfloat16 (liblookahead_hip.so), 1 = float16 (liblookahead_hip_f16.so, the
  * dtype the reference's examples and benchmarks run, lookahead/benchmarks/llama_benchmark.py:27).  The two libraries are the same
@@ -304,6 +304,16 @@ int la_gemm64_swiglu(void* stream, const void* d_wp_gateup, const void* d_xp, in
 int la_gemm64_qkv(void* stream, const void* d_wp, const void* d_xp, int n_heads, int n_kv_heads, int K,
                   const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
                   void* d_qf, void* d_kfresh, void* d_vfresh, int variant);
+/* q/k/v projection bias (Qwen2 / Qwen1.5 / Qwen2.5: q_proj, k_proj, v_proj carry one; models/qwen2/modeling_qwen2.py:234-237).  The
+ * *_bias entry points take the same arguments plus d_bias: NULL (= the entry point without the suffix, bit for bit) or ONE
+ * lane-ordered vector of the storage type, d_bias[(n_heads + 2 * n_kv_heads) * 128] at index slot * 128 + lane (slot = [q heads |
+ * k heads | v heads], lane = the 128-feature lane of la_head_lane_map, zero on padding lanes), 8-byte aligned.  It does not depend on
+ * la_qkv_row_perm / la_rowplan / the image, so one vector serves every form.  Every QKV epilogue adds it in fp32 to the accumulator
+ * before the rounding to the storage type (V rows too; after the sum of the K splits in la_qkv_post), then applies RoPE: F.linear
+ * with a bias followed by apply_rotary_pos_emb. */
+int la_gemm64_qkv_bias(void* stream, const void* d_wp, const void* d_xp, int n_heads, int n_kv_heads, int K,
+                       const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
+                       void* d_qf, void* d_kfresh, void* d_vfresh, int variant, const void* d_bias);
 int la_qkv_row_perm(int n_heads, int n_kv_heads, int32_t* perm /*[(nh+2*nkv)*128], host*/);
 /* Heads narrower than 128 features (LlamaAttention is shape-generic, models/llama/modeling_llama.py:189-308): every kernel of this library
  * lays a head out as a 128-feature LANE (RoPE pairs (d, d + 64), 8192-element Q / K / V fragments, o_proj's K = n_heads * 128).  A model
@@ -333,6 +343,9 @@ int la_gemm64r_logits(void* stream, const void* d_wp, const void* d_xp, int V, i
 int la_gemm64r_qkv(void* stream, const void* d_wp, const void* d_xp, int n_heads, int n_kv_heads, int K, int n_wg,
                    const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
                    void* d_qf, void* d_kfresh, void* d_vfresh);
+int la_gemm64r_qkv_bias(void* stream, const void* d_wp, const void* d_xp, int n_heads, int n_kv_heads, int K, int n_wg,
+                        const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
+                        void* d_qf, void* d_kfresh, void* d_vfresh, const void* d_bias);
 int la_gemm64_logits(void* stream, const void* d_wp, const void* d_xp, int V, int K, int rb,
                      void* d_logits_bf16 /*[64][V] or NULL*/, float* d_cand_val, int32_t* d_cand_idx);
 int la_argmax_finalize(void* stream, const float* d_cand_val, const int32_t* d_cand_idx, int n_tiles,
@@ -346,6 +359,9 @@ int la_resid_norm(void* stream, void* d_h, const float* d_slabs, int n_slabs, co
 int la_qkv_post(void* stream, const float* d_slabs, int n_slabs, int n_heads, int n_kv_heads,
                 const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
                 void* d_qf, void* d_kfresh, void* d_vfresh);
+int la_qkv_post_bias(void* stream, const float* d_slabs, int n_slabs, int n_heads, int n_kv_heads,
+                     const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
+                     void* d_qf, void* d_kfresh, void* d_vfresh, const void* d_bias);
 /* Tree attention: mask-free prefix from the packed main cache + 64 fresh keys under rowmask. */
 int la_tree_attn(void* stream, const void* d_qf, const void* d_kmain, const void* d_vmain,
                  const void* d_kfresh, const void* d_vfresh, const uint64_t* d_rowmask,
@@ -407,6 +423,8 @@ typedef struct la_llama_layer_weights {   /* device pointers, packed by la_pack_
                                         experts of a stage run in ONE launch, otherwise one launch per expert             */
     const void* const* ex_down;      /* host array [n_experts]: packed w2 of each expert                        */
     const void* wqkv_mb;             /* cfg.qkv_mb_wg > 0: the QKV rows once more, planned for cfg.qkv_mb_wg workgroups (multi-block step) */
+    const void* qkv_bias;            /* NULL = no bias (Llama, Mistral, Mixtral); Qwen2: the lane-ordered q/k/v bias of la_gemm64_qkv_bias,
+                                        [(nh+2*nkv)*128] in the storage type, 8-byte aligned — every step entry point adds it in its QKV launch */
 } la_llama_layer_weights;
 
 typedef struct la_llama_weights {
@@ -599,6 +617,11 @@ int la_mb_gemm(void* stream, int kind, const void* d_wp, const void* d_xp, int N
                float* d_slabs, int slab_rows, void* d_act_xp, void* d_logits, float* d_cand_val, int32_t* d_cand_idx,
                const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin, void* d_qf, void* d_kfresh, void* d_vfresh,
                int n_heads, int n_kv_heads);
+/* ... with the q/k/v bias (kind 2 only; any other kind with a bias is LA_E_ARG): see la_gemm64_qkv_bias. */
+int la_mb_gemm_bias(void* stream, int kind, const void* d_wp, const void* d_xp, int N, int K, int nblk, int n_wg, int ksplit,
+                    float* d_slabs, int slab_rows, void* d_act_xp, void* d_logits, float* d_cand_val, int32_t* d_cand_idx,
+                    const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin, void* d_qf, void* d_kfresh, void* d_vfresh,
+                    int n_heads, int n_kv_heads, const void* d_bias);
 /* Set a slot's committed-key cursor (slot 0 = also the single-sequence cursor LA_ST_NKEYS); synchronises the stream. */
 int la_llama_set_nkeys(la_llama* m, void* stream, int slot, int nkeys);
 

@@ -19,7 +19,7 @@ LIB_PATH_F16 = LAB_PATH_F16 if LAB_BUILD else os.path.join(_HERE, "liblookahead_
 LA_DTYPE_BF16, LA_DTYPE_F16 = 0, 1
 
 LA_OK = 0
-ABI_VERSION = 12        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
+ABI_VERSION = 13        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
 LA_MODE_INPUT, LA_MODE_OUTPUT, LA_MODE_MIX = 0, 1, 2
 LA_TREE_MAX = 64
 LA_MOE_MAX_E = 8
@@ -91,7 +91,8 @@ class LlamaConfigC(C.Structure):
 
 class LlamaLayerWeightsC(C.Structure):
     _fields_ = [("wqkv", vp), ("wo", vp), ("wgateup", vp), ("wdown", vp), ("norm1", vp), ("norm2", vp),
-                ("router", vp), ("ex_gateup", C.POINTER(vp)), ("ex_down", C.POINTER(vp)), ("wqkv_mb", vp)]
+                ("router", vp), ("ex_gateup", C.POINTER(vp)), ("ex_down", C.POINTER(vp)), ("wqkv_mb", vp),
+                ("qkv_bias", vp)]
 
 
 class LlamaWeightsC(C.Structure):
@@ -169,6 +170,7 @@ PROTOTYPES = {
     "la_gemm64_slab": (i32, vp, vp, vp, i32, i32, i32, i32, vp),
     "la_gemm64_swiglu": (i32, vp, vp, vp, i32, i32, vp, i32),
     "la_gemm64_qkv": (i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32),
+    "la_gemm64_qkv_bias": (i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp),
     "la_qkv_row_perm": (i32, i32, i32, pi32),
     "la_head_lane_map": (i32, i32, pi32),
     "la_rowplan": (i32, i32, i32, i32, pi32),
@@ -177,11 +179,13 @@ PROTOTYPES = {
     "la_gemm64r_swiglu": (i32, vp, vp, vp, i32, i32, i32, vp),
     "la_gemm64r_logits": (i32, vp, vp, vp, i32, i32, i32, vp, vp, vp),
     "la_gemm64r_qkv": (i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp),
+    "la_gemm64r_qkv_bias": (i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp),
     "la_gemm64_logits": (i32, vp, vp, vp, i32, i32, i32, vp, vp, vp),
     "la_argmax_finalize": (i32, vp, vp, vp, i32, vp),
     "la_embed_norm": (i32, vp, vp, vp, vp, i32, f32, vp, vp),
     "la_resid_norm": (i32, vp, vp, vp, i32, vp, i32, f32, vp),
     "la_qkv_post": (i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp),
+    "la_qkv_post_bias": (i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp),
     "la_tree_attn": (i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp),
     "la_llama_workspace_bytes": (i64, C.POINTER(LlamaConfigC)),
     "la_llama_create": (vp, C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, i64),
@@ -228,6 +232,7 @@ PROTOTYPES = {
     "la_comm_destroy": (i32, vp),
     "la_gather_accepted": (i32, vp, vp, vp, i32, i32, vp),
     "la_mb_gemm": (i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32),
+    "la_mb_gemm_bias": (i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp),
     "la_llama_bstep_eager": (i32, vp, vp, vp, vp),
     "la_llama_reset_slot": (i32, vp, vp, i32),
 }

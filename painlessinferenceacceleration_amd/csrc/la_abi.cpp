@@ -20,14 +20,23 @@ int la_abi_version(void) { return LA_ABI_VERSION; }
 int la_abi_dtype(void) { return LA_DTYPE; }
 const char* la_last_error(void) { return g_err.c_str(); }
 extern int g_la_stop_layers, g_la_graph_epoch;
-int la_mb_gemm(void* stream, int kind, const void* wp, const void* xp, int N, int K, int nblk, int n_wg, int ksplit,
-               float* slabs, int slab_rows, void* act_xp, void* logits, float* cand_val, int32_t* cand_idx, const int32_t* pos,
-               const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, int nh, int nkv) {
-    if (!wp || !xp) return LA_E_ARG;
+// the q/k/v bias vector is read with up to 8-byte loads (qkv_bias_add, la_common.h)
+static bool bias_ok(const void* b) { return ((uintptr_t)b & 7) == 0; }
+int la_mb_gemm_bias(void* stream, int kind, const void* wp, const void* xp, int N, int K, int nblk, int n_wg, int ksplit,
+                    float* slabs, int slab_rows, void* act_xp, void* logits, float* cand_val, int32_t* cand_idx, const int32_t* pos,
+                    const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, int nh, int nkv, const void* d_bias) {
+    if (!wp || !xp || !bias_ok(d_bias) || (d_bias && kind != 2)) return LA_E_ARG;
     MbGemm g{}; g.wp = wp; g.xp = xp; g.N = N; g.K = K; g.nblk = nblk; g.n_wg = n_wg; g.ksplit = ksplit;
     g.slabs = slabs; g.slab_rows = slab_rows; g.act_xp = act_xp; g.logits = logits; g.cand_val = cand_val; g.cand_idx = cand_idx;
     g.pos = pos; g.rcos = rcos; g.rsin = rsin; g.qf = qf; g.kfresh = kfresh; g.vfresh = vfresh; g.nh = nh; g.nkv = nkv;
+    g.qkv_bias = d_bias;
     WRAP(lk_mb_gemm((hipStream_t)stream, kind, g));
+}
+int la_mb_gemm(void* stream, int kind, const void* wp, const void* xp, int N, int K, int nblk, int n_wg, int ksplit,
+               float* slabs, int slab_rows, void* act_xp, void* logits, float* cand_val, int32_t* cand_idx, const int32_t* pos,
+               const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, int nh, int nkv) {
+    return la_mb_gemm_bias(stream, kind, wp, xp, N, K, nblk, n_wg, ksplit, slabs, slab_rows, act_xp, logits, cand_val, cand_idx, pos,
+                           rcos, rsin, qf, kfresh, vfresh, nh, nkv, nullptr);
 }
 // The product header keeps ONE debug key: 13 = depth probe of the parity tests (the step runs the first n layers, then the final
 // norm + lm_head).  The measurement knobs / A/B switches are la_lab_* (la_lab.cpp, include/lookahead_hip_lab.h).
@@ -67,10 +76,14 @@ int la_gemm64_swiglu(void* stream, const void* wp, const void* xp, int F, int K,
     if (!wp || !xp || !act || F % 32 || K % 16) return LA_E_ARG;
     WRAP(lk_gemm64_swiglu((hipStream_t)stream, wp, xp, F, K, act, variant));
 }
+int la_gemm64_qkv_bias(void* stream, const void* wp, const void* xp, int nh, int nkv, int K, const int32_t* pos, const void* rcos,
+                       const void* rsin, void* qf, void* kf, void* vf, int variant, const void* d_bias) {
+    if (!wp || !xp || !pos || !rcos || !rsin || !qf || !kf || !vf || nh <= 0 || nkv <= 0 || K % 16 || !bias_ok(d_bias)) return LA_E_ARG;
+    WRAP(lk_gemm64_qkv((hipStream_t)stream, wp, xp, nh, nkv, K, pos, rcos, rsin, qf, kf, vf, variant, d_bias));
+}
 int la_gemm64_qkv(void* stream, const void* wp, const void* xp, int nh, int nkv, int K, const int32_t* pos, const void* rcos,
                   const void* rsin, void* qf, void* kf, void* vf, int variant) {
-    if (!wp || !xp || !pos || !rcos || !rsin || !qf || !kf || !vf || nh <= 0 || nkv <= 0 || K % 16) return LA_E_ARG;
-    WRAP(lk_gemm64_qkv((hipStream_t)stream, wp, xp, nh, nkv, K, pos, rcos, rsin, qf, kf, vf, variant));
+    return la_gemm64_qkv_bias(stream, wp, xp, nh, nkv, K, pos, rcos, rsin, qf, kf, vf, variant, nullptr);
 }
 int la_qkv_row_perm(int nh, int nkv, int32_t* perm) {
     if (!perm || nh <= 0 || nkv <= 0) return LA_E_ARG;
@@ -111,11 +124,16 @@ int la_gemm64r_logits(void* stream, const void* wp, const void* xp, int V, int K
     if (lk_gemm64r_init() != 0) return LA_E_HIP;
     WRAP(lk_gemm64r_logits((hipStream_t)stream, wp, xp, V, K, n_wg, logits, cv, ci));
 }
+int la_gemm64r_qkv_bias(void* stream, const void* wp, const void* xp, int nh, int nkv, int K, int n_wg, const int32_t* pos,
+                        const void* rcos, const void* rsin, void* qf, void* kf, void* vf, const void* d_bias) {
+    if (!wp || !xp || !pos || !rcos || !rsin || !qf || !kf || !vf || nh <= 0 || nkv <= 0 || K % 16 || n_wg <= 0 || !bias_ok(d_bias))
+        return LA_E_ARG;
+    if (lk_gemm64r_init() != 0) return LA_E_HIP;
+    WRAP(lk_gemm64r_qkv((hipStream_t)stream, wp, xp, nh, nkv, K, n_wg, pos, rcos, rsin, qf, kf, vf, nullptr, d_bias));
+}
 int la_gemm64r_qkv(void* stream, const void* wp, const void* xp, int nh, int nkv, int K, int n_wg, const int32_t* pos,
                    const void* rcos, const void* rsin, void* qf, void* kf, void* vf) {
-    if (!wp || !xp || !pos || !rcos || !rsin || !qf || !kf || !vf || nh <= 0 || nkv <= 0 || K % 16 || n_wg <= 0) return LA_E_ARG;
-    if (lk_gemm64r_init() != 0) return LA_E_HIP;
-    WRAP(lk_gemm64r_qkv((hipStream_t)stream, wp, xp, nh, nkv, K, n_wg, pos, rcos, rsin, qf, kf, vf));
+    return la_gemm64r_qkv_bias(stream, wp, xp, nh, nkv, K, n_wg, pos, rcos, rsin, qf, kf, vf, nullptr);
 }
 int la_gemm64_logits(void* stream, const void* wp, const void* xp, int V, int K, int rb, void* logits, float* cv,
                      int32_t* ci) {
@@ -136,10 +154,14 @@ int la_resid_norm(void* stream, void* h, const float* slabs, int n_slabs, const 
     if (!h || !nw || !xp || n_slabs < 0 || (n_slabs > 0 && !slabs)) return LA_E_ARG;
     WRAP(lk_resid_norm((hipStream_t)stream, h, slabs, n_slabs, nw, hidden, eps, xp));
 }
+int la_qkv_post_bias(void* stream, const float* slabs, int n_slabs, int nh, int nkv, const int32_t* pos, const void* rcos,
+                     const void* rsin, void* qf, void* kf, void* vf, const void* d_bias) {
+    if (!slabs || n_slabs < 1 || nh <= 0 || nkv <= 0 || !pos || !rcos || !rsin || !qf || !kf || !vf || !bias_ok(d_bias)) return LA_E_ARG;
+    WRAP(lk_qkv_post((hipStream_t)stream, slabs, n_slabs, nh, nkv, pos, rcos, rsin, qf, kf, vf, d_bias));
+}
 int la_qkv_post(void* stream, const float* slabs, int n_slabs, int nh, int nkv, const int32_t* pos, const void* rcos,
                 const void* rsin, void* qf, void* kf, void* vf) {
-    if (!slabs || n_slabs < 1 || nh <= 0 || nkv <= 0 || !pos || !rcos || !rsin || !qf || !kf || !vf) return LA_E_ARG;
-    WRAP(lk_qkv_post((hipStream_t)stream, slabs, n_slabs, nh, nkv, pos, rcos, rsin, qf, kf, vf));
+    return la_qkv_post_bias(stream, slabs, n_slabs, nh, nkv, pos, rcos, rsin, qf, kf, vf, nullptr);
 }
 int la_tree_attn(void* stream, const void* qf, const void* km, const void* vm, const void* kf, const void* vf,
                  const uint64_t* rowmask, const int32_t* d_state, int nh, int nkv, int max_keys, int nsplit,

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <math.h>
+#include <type_traits>
 
 // Storage / MFMA-input type of THIS build of the library.  Every kernel is written once; the build compiles the sources twice:
 //   LA_DTYPE 0 -> liblookahead_hip.so      bfloat16, v_mfma_f32_32x32x16_bf16 (BASELINE's dtype)
@@ -57,6 +58,29 @@ __device__ __forceinline__ bf16_t f2bf_int(float f) {
     return (bf16_t)((nan ? (u | 0x400000u) : r) >> 16);
 }
 __device__ __forceinline__ float bfr(float f) { return bf2f(f2bf(f)); }
+// q / k / v projection bias (Qwen2: modeling_qwen2.py:234-237) in every QKV epilogue.  ONE lane-ordered vector per layer,
+// bias[(nh + 2 * nkv) * 128] in the storage type at index slot * 128 + lane (slot = [q heads | k heads | v heads], lane = the
+// 128-feature lane of la_head_lane_map, zero on padding lanes), whatever row order the weight image has.  v[o .. o + N) +=
+// bias[i .. i + N) in fp32 BEFORE the accumulator is rounded to the storage type (F.linear with a bias: fp32 epilogue, one
+// rounding); N = 4 / 2 / 1 lanes in one 8 / 4 / 2-byte load, the width the site stores (N = 1 also takes a scalar v).
+// A null bias (Llama, Mistral, Mixtral) is a wave-uniform skip: nothing is loaded or added.  (An accumulator that starts at +0
+// never becomes -0, so even an all-zero bias leaves every value unchanged bit for bit.)
+template <int N, typename V>
+__device__ __forceinline__ void qkv_bias_add(const bf16_t* __restrict__ bias, int i, V& v, int o = 0) {
+    if (bias == nullptr) return;
+    if constexpr (N == 4) {
+        const uint2 w = *(const uint2*)(bias + i);
+        v[o] += bf2f((bf16_t)w.x); v[o + 1] += bf2f((bf16_t)(w.x >> 16));
+        v[o + 2] += bf2f((bf16_t)w.y); v[o + 3] += bf2f((bf16_t)(w.y >> 16));
+    } else if constexpr (N == 2) {
+        const uint32_t w = *(const uint32_t*)(bias + i);
+        v[o] += bf2f((bf16_t)w); v[o + 1] += bf2f((bf16_t)(w >> 16));
+    } else {
+        static_assert(N == 1, "4, 2 or 1 lanes per load");
+        if constexpr (std::is_arithmetic<V>::value) v += bf2f(bias[i]);      // a scalar site
+        else v[o] += bf2f(bias[i]);
+    }
+}
 // the 32x32x16 MFMA of the build's storage type (identical operand layouts): LA_MFMA(a, b, c, 0, 0, 0)
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 #if LA_DTYPE == 1

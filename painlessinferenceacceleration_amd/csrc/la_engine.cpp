@@ -298,6 +298,8 @@ extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_
     m->w = *w;
     m->layers.assign(w->layers, w->layers + cfg->n_layers);
     m->w.layers = m->layers.data();
+    for (int l = 0; l < cfg->n_layers; ++l)
+        if ((uintptr_t)w->layers[l].qkv_bias & 7) { la_set_error("qkv_bias must be 8-byte aligned"); delete m; return nullptr; }
     if (cfg->n_experts > 0) {
         for (int l = 0; l < cfg->n_layers; ++l) {
             const la_llama_layer_weights& L = w->layers[l];
@@ -454,15 +456,15 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
             // layers > 0: the input norm (residual + down-projection slabs of the previous layer) runs inside this launch
             FusedNorm fq{m->slabs, m->down_ks, m->h, L.norm1, c.hidden, c.rms_eps, cf, m->fuse_cnt + 2 * l, (m->fuse & 16) ? 1 : 0};
             KCHK(lk_gemm64r_qkv(st, L.wqkv, m->xp, c.n_heads, c.n_kv_heads, c.hidden, c.balanced_wg[0], m->pos,
-                                m->w.rope_cos, m->w.rope_sin, m->qf, kf, vf, ((m->fuse & 2) && l > 0) ? &fq : nullptr));
+                                m->w.rope_cos, m->w.rope_sin, m->qf, kf, vf, ((m->fuse & 2) && l > 0) ? &fq : nullptr, L.qkv_bias));
         } else if (m->qkv_fused) {
             KCHK(lk_gemm64_qkv(st, L.wqkv, m->xp, c.n_heads, c.n_kv_heads, c.hidden, m->pos, m->w.rope_cos, m->w.rope_sin,
-                               m->qf, kf, vf, m->qkv_rb >> 8));
+                               m->qf, kf, vf, m->qkv_rb >> 8, L.qkv_bias));
         } else {
             KCHK(lk_gemm64_slab(st, L.wqkv, m->xp, m->qkv_n, c.hidden, m->qkv_rb, m->qkv_ks, m->slabs));
             P(KC_OTHER);
             KCHK(lk_qkv_post(st, m->slabs, m->qkv_ks, c.n_heads, c.n_kv_heads, m->pos, m->w.rope_cos, m->w.rope_sin,
-                             m->qf, kf, vf));
+                             m->qf, kf, vf, L.qkv_bias));
         }
         P(KC_ATTN);
         if (fork && c.n_experts == 0) {
@@ -747,7 +749,7 @@ static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = fals
         const bool mbq = c.qkv_mb_wg > 0 && L.wqkv_mb && nblk >= 3;
         q.wp = mbq ? L.wqkv_mb : L.wqkv; q.n_wg = mbq ? c.qkv_mb_wg : c.balanced_wg[0];
         q.pos = m->mb_pos; q.rcos = m->w.rope_cos; q.rsin = m->w.rope_sin; q.qf = m->mb_qf; q.kfresh = kf; q.vfresh = vf;
-        q.nh = c.n_heads; q.nkv = c.n_kv_heads;
+        q.nh = c.n_heads; q.nkv = c.n_kv_heads; q.qkv_bias = L.qkv_bias;
         KCHK(lk_mb_gemm(st, 2, q));
         KCHK(lk_mb_tree_attn(st, m->mb_qf, m->kmain + (size_t)l * m->kv_layer_elems, m->vmain + (size_t)l * m->kv_layer_elems, kf, vf,
                              m->mb_rowmask, m->mb_meta, nblk, c.n_heads, c.n_kv_heads, c.max_keys, m->n_slots, mb_split(nblk, c.n_heads, c.balanced_wg[1] > 0 ? c.balanced_wg[1] : 256),

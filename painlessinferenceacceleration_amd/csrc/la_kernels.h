@@ -45,7 +45,7 @@ int lk_gemm64_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int 
 int lk_gemm64_logits(hipStream_t st, const void* wp, const void* xp, int V, int K, int rb, void* logits, float* cv, int* ci);
 int lk_logits_cand_slots(int V, int rbv);
 int lk_gemm64_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, const int* pos, const void* rcos,
-                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant);
+                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant, const void* qkv_bias = nullptr);
 void lk_qkv_row_perm(int nh, int nkv, int* perm);
 int lk_gemm64r_init();
 int lk_step_head(hipStream_t st, const int* in, int* state, int* pos, uint64_t* rowmask, int* ids, const void* embed, const void* nw,
@@ -63,7 +63,8 @@ int lk_gemm64r_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int
                       const float* route_col = nullptr, const FusedNorm* fn = nullptr, const PfDesc* pf = nullptr);
 int lk_gemm64r_logits(hipStream_t st, const void* wp, const void* xp, int V, int K, int n_wg, void* logits, float* cv, int* ci);
 int lk_gemm64r_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, int n_wg, const int* pos,
-                   const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn = nullptr);
+                   const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn = nullptr,
+                   const void* qkv_bias = nullptr);
 int lk_argmax_finalize(hipStream_t st, const float* cv, const int* ci, int n_tiles, int* out_rows);
 int lk_embed_norm(hipStream_t st, const void* embed, const int* ids, const void* nw, int hidden, float eps, void* h, void* xp,
                   int cast_first = 0, const PfDesc* pf = nullptr);
@@ -77,7 +78,7 @@ int lk_resid_norm_addend(hipStream_t st, void* h, const void* addend, const void
 int lk_moe_accum(hipStream_t st, const float* slabs, int n_slabs, const float* route_col, int hidden, void* acc, int first);
 int lk_build_tree_inputs(hipStream_t st, const int* in, int* state, int* pos, uint64_t* rowmask, int* ids);
 int lk_qkv_post(hipStream_t st, const float* slabs, int n_slabs, int nh, int nkv, const int* pos, const void* rcos,
-                const void* rsin, void* qf, void* kfresh, void* vfresh);
+                const void* rsin, void* qf, void* kfresh, void* vfresh, const void* qkv_bias = nullptr);
 int lk_tree_attn(hipStream_t st, const void* qf, const void* kmain, const void* vmain, const void* kfresh,
                  const void* vfresh, const uint64_t* rowmask, const int* state, int nh, int nkv, int max_keys,
                  int nsplit, float* opart, float* mpart, float* lpart, void* attn_xp, int window = 0, int ring_keys = 0,

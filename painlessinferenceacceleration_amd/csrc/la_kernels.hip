@@ -358,6 +358,7 @@ struct GemmArgs {
     bf16_t* kfresh;
     bf16_t* vfresh;
     int nh, nkv;
+    const bf16_t* qkv_bias;     // null, or the lane-ordered q/k/v bias (qkv_bias_add, la_common.h)
     // mixture-of-experts: routing weights of this expert, one float per token row at stride LA_MOE_MAX_E; the whole
     // launch returns at once when no row routes to the expert (its weights are then never read)
     const float* route_col;
@@ -599,6 +600,8 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
 #pragma unroll
         for (int gg = 0; gg < GPW; ++gg) {
             const int dlo = 32 * u + 8 * (g0 + gg) + 4 * hh, dhi = dlo + 64;
+            qkv_bias_add<4>(a.qkv_bias, slot * 128 + dlo, fin[0][gg]);
+            qkv_bias_add<4>(a.qkv_bias, slot * 128 + dhi, fin[RB - 1][gg]);
             if (slot < a.nh + a.nkv) {
                 bf16_t* dst = slot < a.nh ? a.qf + (size_t)slot * 8192 : a.kfresh + (size_t)(slot - a.nh) * 8192;
                 bf16x4 olo, ohi;
@@ -861,6 +864,8 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                 xl += red4[(((tbe * NW + p) * RB + 0) * 4 + gi) * 64 + lane];
                 xh += red4[(((tbe * NW + p) * RB + 1) * 4 + gi) * 64 + lane];
             }
+            qkv_bias_add<4>(a.qkv_bias, slot * 128 + dlo, xl);
+            qkv_bias_add<4>(a.qkv_bias, slot * 128 + dhi, xh);
             if (rope) {
                 bf16_t* dst = slot < a.nh ? a.qf + (size_t)slot * 8192 : a.kfresh + (size_t)(slot - a.nh) * 8192;
                 bf16x4 olo, ohi;
@@ -937,7 +942,9 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                     const int f = 8 * gi + 4 * hh + j;
                     if (f < ra.nv[0]) {
                         const int pr = ra.R * bp.bx + f, slot = pr >> 6, dlo = pr & 63, dhi = dlo + 64;
-                        const float xl = xl4[j], xh = xh4[j];
+                        float xl = xl4[j], xh = xh4[j];
+                        qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
+                        qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
                         if (slot < a.nh + a.nkv) {
                             bf16_t* dst = slot < a.nh ? a.qf + (size_t)slot * 8192 : a.kfresh + (size_t)(slot - a.nh) * 8192;
                             const float c = bf2f(a.rcos[(size_t)ps * 64 + dlo]), sn = bf2f(a.rsin[(size_t)ps * 64 + dlo]);
@@ -1145,7 +1152,8 @@ template <int NS>
 __global__ __launch_bounds__(256) void k_qkv_post(const float* __restrict__ slabs, int nh, int nkv,
                                                    const int* __restrict__ pos, const bf16_t* __restrict__ rcos,
                                                    const bf16_t* __restrict__ rsin, bf16_t* __restrict__ qf,
-                                                   bf16_t* __restrict__ kfresh, bf16_t* __restrict__ vfresh) {
+                                                   bf16_t* __restrict__ kfresh, bf16_t* __restrict__ vfresh,
+                                                   const bf16_t* __restrict__ qkv_bias) {
     __shared__ __attribute__((aligned(16))) bf16_t sh[LA_TB][128 + 8];
     const int slot = blockIdx.x;
     const int N = (nh + 2 * nkv) * 128;
@@ -1170,6 +1178,7 @@ __global__ __launch_bounds__(256) void k_qkv_post(const float* __restrict__ slab
         acc[j] = *(const f32x4*)(slabs + (size_t)t * N + slot * 128 + c4);
 #pragma unroll
         for (int sl = 1; sl < NS; ++sl) acc[j] += *(const f32x4*)(slabs + ((size_t)sl * LA_TB + t) * N + slot * 128 + c4);
+        qkv_bias_add<4>(qkv_bias, slot * 128 + c4, acc[j]);        // once, to the sum of the K splits
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -1944,10 +1953,12 @@ int lk_gemm64_logits(hipStream_t st, const void* wp, const void* xp, int V, int 
 }
 // QKV projection with the RoPE / fragment epilogue.  wp must be packed from the row-permuted [Wq;Wk;Wv] (lk_qkv_row_perm).
 int lk_gemm64_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, const int* pos, const void* rcos,
-                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant) {
+                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant, const void* qkv_bias) {
+    if (qkv_bias && g_la_dbg_noepi) return -1;          // the timing probe writes no epilogue: it would drop the bias
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = (nh + 2 * nkv) * 128;
     a.pos = pos; a.rcos = (const bf16_t*)rcos; a.rsin = (const bf16_t*)rsin;
     a.qf = (bf16_t*)qf; a.kfresh = (bf16_t*)kfresh; a.vfresh = (bf16_t*)vfresh; a.nh = nh; a.nkv = nkv;
+    a.qkv_bias = (const bf16_t*)qkv_bias;
     return launch_gemm<2, EPI_QKV>(st, a, a.N / 64, 1, variant);
 }
 // packed row r of the permuted QKV matrix <- original row perm[r]: workgroup b = r/64 holds head slot b>>1, dims
@@ -2074,10 +2085,12 @@ int lk_gemm64r_logits(hipStream_t st, const void* wp, const void* xp, int V, int
     LAUNCH_CHECK(); return 0;
 }
 int lk_gemm64r_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, int n_wg, const int* pos,
-                   const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn) {
+                   const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn, const void* qkv_bias) {
+    if (qkv_bias && g_la_dbg_noepi) return -1;          // the timing probe writes no epilogue: it would drop the bias
     GemmRArgs ra{}; ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times; ra.g.wp = (const bf16_t*)wp; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = (nh + 2 * nkv) * 128;
     ra.g.pos = pos; ra.g.rcos = (const bf16_t*)rcos; ra.g.rsin = (const bf16_t*)rsin;
     ra.g.qf = (bf16_t*)qf; ra.g.kfresh = (bf16_t*)kfresh; ra.g.vfresh = (bf16_t*)vfresh; ra.g.nh = nh; ra.g.nkv = nkv;
+    ra.g.qkv_bias = (const bf16_t*)qkv_bias;
     const int pairs = (nh + 2 * nkv) * 64;
     ra.R = pairs / n_wg; if (pairs % n_wg || ra.R > 32) return -1;
     ra.nv[0] = ra.nv[1] = ra.R;
@@ -2241,9 +2254,9 @@ int lk_build_tree_inputs(hipStream_t st, const int* in, int* state, int* pos, ui
     LAUNCH_CHECK(); return 0;
 }
 int lk_qkv_post(hipStream_t st, const float* slabs, int n_slabs, int nh, int nkv, const int* pos, const void* rcos,
-                const void* rsin, void* qf, void* kfresh, void* vfresh) {
+                const void* rsin, void* qf, void* kfresh, void* vfresh, const void* qkv_bias) {
 #define QP(NS) k_qkv_post<NS><<<nh + 2 * nkv, 256, 0, st>>>(slabs, nh, nkv, pos, (const bf16_t*)rcos, (const bf16_t*)rsin, \
-                                                          (bf16_t*)qf, (bf16_t*)kfresh, (bf16_t*)vfresh)
+                                                          (bf16_t*)qf, (bf16_t*)kfresh, (bf16_t*)vfresh, (const bf16_t*)qkv_bias)
     switch (n_slabs) {
         case 1: QP(1); break; case 2: QP(2); break; case 3: QP(3); break; case 4: QP(4); break; case 8: QP(8); break;
         default: return -1;

@@ -37,6 +37,7 @@ struct MbGemm {
     void* act_xp;
     void* logits; float* cand_val; int* cand_idx;
     const int* pos; const void* rcos; const void* rsin; void* qf; void* kfresh; void* vfresh; int nh, nkv;
+    const void* qkv_bias;              // kind 2: null, or the lane-ordered q/k/v bias (qkv_bias_add, la_common.h)
     const float* route_col;            // MoE: this expert's routing weights (stride LA_MOE_MAX_E floats per row); null = dense
     const int* nblk_dev;               // gathered MoE: the expert's block count on the device (nblk = the upper bound); null = nblk
     // gathered MoE, ALL experts of a stage in one launch (ex_n > 1, needs nblk_dev): expert e reads wp + e * ex_w_stride, xp + e *

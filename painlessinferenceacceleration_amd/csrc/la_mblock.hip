@@ -51,6 +51,7 @@ struct MbArgs {
     int* cand_idx;
     const int* pos; const bf16_t* rcos; const bf16_t* rsin;      // MB_QKV
     bf16_t* qf; bf16_t* kfresh; bf16_t* vfresh; int nh, nkv;
+    const bf16_t* qkv_bias;  // MB_QKV: null, or the lane-ordered q/k/v bias (qkv_bias_add, la_common.h)
     // mixture-of-experts: routing weights of THIS expert, one float per row at stride LA_MOE_MAX_E; when no row of the step routes
     // to the expert the launch returns at once and its weights are never read
     const float* route_col; int route_rows;
@@ -130,7 +131,9 @@ __device__ __forceinline__ void mb_epilogue_block(const MbArgs& a, const f32x4* 
                 const int f = 8 * gi + 4 * hh + j;
                 if (f < a.nv[0]) {
                     const int prr = a.R * blockIdx.x + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
-                    const float xl = xl4[j], xh = xh4[j];
+                    float xl = xl4[j], xh = xh4[j];
+                    qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
+                    qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
                     if (slot < a.nh + a.nkv) {
                         bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                                   : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
@@ -739,6 +742,8 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                     const int f = 8 * (i >> 2) + 4 * hh;
                     if (f < a.nv[0]) {
                         const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
+                        qkv_bias_add<4>(a.qkv_bias, slot * 128 + dlo, acc[0][t], i);
+                        qkv_bias_add<4>(a.qkv_bias, slot * 128 + dhi, acc[1][t], i);
                         if (slot < a.nh + a.nkv) {
                             bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                                       : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
@@ -773,6 +778,8 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                     const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
                     if (f < a.nv[0]) {
                         const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
+                        qkv_bias_add<2>(a.qkv_bias, slot * 128 + dlo, acc[0][t], i);
+                        qkv_bias_add<2>(a.qkv_bias, slot * 128 + dhi, acc[1][t], i);
                         if (slot < a.nh + a.nkv) {
                             bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                                       : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
@@ -803,7 +810,9 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                     const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
                     if (f < a.nv[0]) {
                         const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
-                        const float xl = acc[0][t][i], xh = acc[1][t][i];
+                        float xl = acc[0][t][i], xh = acc[1][t][i];
+                        qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
+                        qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
                         if (slot < a.nh + a.nkv) {
                             bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                                       : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
@@ -905,7 +914,7 @@ template <int RBV, int TW, int RPW_ = 4> struct FatGeom {
 // apply_rotary_pos_emb, modeling_llama.py:154-169, in bf16 arithmetic; V rows pass through)
 // RV = rows a lane handles per store: 4 (R % 4 == 0: 8-byte table loads and fragment stores), 2 (R even: 4-byte), 1 (any R)
 template <int RV>
-__device__ __forceinline__ void fat_qkv_tile(const MbArgs& a, const f32x16& lo, const f32x16& hi, int region, int blk, int tok, int hh) {
+__device__ __forceinline__ void fat_qkv_tile(const MbArgs& a, f32x16 lo, f32x16 hi, int region, int blk, int tok, int hh) {
     const int ps = a.pos[blk * 64 + tok];
     if constexpr (RV == 4) {
 #pragma unroll
@@ -914,6 +923,8 @@ __device__ __forceinline__ void fat_qkv_tile(const MbArgs& a, const f32x16& lo, 
             const int f = 8 * (i >> 2) + 4 * hh;
             if (f < a.nv[0]) {
                 const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
+                qkv_bias_add<4>(a.qkv_bias, slot * 128 + dlo, lo, i);
+                qkv_bias_add<4>(a.qkv_bias, slot * 128 + dhi, hi, i);
                 if (slot < a.nh + a.nkv) {
                     bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                               : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
@@ -947,6 +958,8 @@ __device__ __forceinline__ void fat_qkv_tile(const MbArgs& a, const f32x16& lo, 
             const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
             if (f < a.nv[0]) {
                 const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
+                qkv_bias_add<2>(a.qkv_bias, slot * 128 + dlo, lo, i);
+                qkv_bias_add<2>(a.qkv_bias, slot * 128 + dhi, hi, i);
                 if (slot < a.nh + a.nkv) {
                     bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                               : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
@@ -977,7 +990,9 @@ __device__ __forceinline__ void fat_qkv_tile(const MbArgs& a, const f32x16& lo, 
             const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
             if (f < a.nv[0]) {
                 const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
-                const float xl = lo[i], xh = hi[i];
+                float xl = lo[i], xh = hi[i];
+                qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
+                qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
                 if (slot < a.nh + a.nkv) {
                     bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                               : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
@@ -3067,6 +3082,8 @@ int lk_mb_gemm(hipStream_t st, int kind, const MbGemm& g) {
     if (kind == 2) {
         a.pos = g.pos; a.rcos = (const bf16_t*)g.rcos; a.rsin = (const bf16_t*)g.rsin;
         a.qf = (bf16_t*)g.qf; a.kfresh = (bf16_t*)g.kfresh; a.vfresh = (bf16_t*)g.vfresh; a.nh = g.nh; a.nkv = g.nkv;
+        a.qkv_bias = (const bf16_t*)g.qkv_bias;
+        if (a.qkv_bias && g_la_mb_dbg == 4) return -1;      // the no-epilogue measurement build would drop the bias
         if (!a.planned) {                          // classic row-permuted image (la_qkv_row_perm): pair index = 32 * workgroup + f
             a.R = 32;
             return launch_mb<2, MB_QKV>(st, a, (g.nh + 2 * g.nkv) * 2, 1, g.nblk);

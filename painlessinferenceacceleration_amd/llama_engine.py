@@ -12,6 +12,7 @@ from lookahead_generation (common/pretrained_model.py:1176-1181).
 """
 import ctypes as C
 import math
+import re
 import os
 
 import numpy as np
@@ -25,8 +26,12 @@ class LlamaShape(object):
     """The fields of LlamaConfig the path uses."""
 
     def __init__(self, n_layers=32, hidden=4096, n_heads=32, n_kv_heads=None, ffn=11008, vocab=32000,
-                 rms_eps=1e-5, rope_theta=10000.0, head_dim=None, n_experts=0, top_k=2, norm_cast_first=False, sliding_window=0):
+                 rms_eps=1e-5, rope_theta=10000.0, head_dim=None, n_experts=0, top_k=2, norm_cast_first=False, sliding_window=0,
+                 qkv_bias=False):
         self.n_layers, self.hidden, self.n_heads = n_layers, hidden, n_heads
+        # Qwen2 (Qwen1.5 / Qwen2 / Qwen2.5): q_proj / k_proj / v_proj carry a bias (qwen2/modeling_qwen2.py:234-237), added in the
+        # fp32 epilogue of every QKV launch; o_proj and the MLP have none
+        self.qkv_bias = bool(qkv_bias)
         self.n_experts, self.top_k = n_experts, top_k       # > 0: Mixtral sparse-MoE MLP
         # RMSNorm flavour: False = LlamaRMSNorm (one rounding), True = Mistral/MixtralRMSNorm (normalised value rounded
         # to the activation dtype before the weight multiply, mixtral/modeling_mixtral.py:160-165)
@@ -54,6 +59,16 @@ class LlamaShape(object):
         return cls(32, 4096, 32, 8, 14336, 32000, 1e-5, rope_theta=1e6, n_experts=8, top_k=2, norm_cast_first=True)
 
     @classmethod
+    def qwen2_7b(cls):
+        """Qwen2.5-7B (Qwen2-7B: the same layer shape)"""
+        return cls(28, 3584, 28, 4, 18944, 152064, 1e-6, rope_theta=1e6, norm_cast_first=True, qkv_bias=True)
+
+    @classmethod
+    def qwen2_0_5b(cls):
+        """Qwen2-0.5B / Qwen2.5-0.5B: head_dim 64, tied embeddings (lm_head = embed_tokens)"""
+        return cls(24, 896, 14, 2, 4864, 151936, 1e-6, rope_theta=1e6, norm_cast_first=True, qkv_bias=True)
+
+    @classmethod
     def from_hf(cls, cfg):
         """LlamaConfig / MistralConfig / MixtralConfig of transformers 4.3x (the reference's pins) or 5.x (rope_theta moved
         into cfg.rope_parameters)."""
@@ -69,13 +84,14 @@ class LlamaShape(object):
                    getattr(cfg, 'num_key_value_heads', None), cfg.intermediate_size, cfg.vocab_size,
                    cfg.rms_norm_eps, float(rope_theta), head_dim=head_dim,
                    n_experts=getattr(cfg, 'num_local_experts', 0) or 0, top_k=getattr(cfg, 'num_experts_per_tok', 2),
-                   norm_cast_first=getattr(cfg, 'model_type', 'llama') in ('mistral', 'mixtral'))
+                   norm_cast_first=getattr(cfg, 'model_type', 'llama') in ('mistral', 'mixtral', 'qwen2'),
+                   qkv_bias=getattr(cfg, 'model_type', 'llama') == 'qwen2')
 
     def n_params_no_embed(self):
         hd = self.head_dim
         mlp = 3 * self.ffn * self.hidden * max(self.n_experts, 1) + self.n_experts * self.hidden
         per_layer = (self.n_heads + 2 * self.n_kv_heads) * hd * self.hidden + self.n_heads * hd * self.hidden \
-            + mlp + 2 * self.hidden
+            + mlp + 2 * self.hidden + (self.n_heads + 2 * self.n_kv_heads) * hd * int(self.qkv_bias)
         return self.n_layers * per_layer + self.hidden + self.vocab * self.hidden
 
 
@@ -173,6 +189,15 @@ def random_weights(shape, seed=0, std=0.02, device='cpu', dtype=torch.bfloat16, 
         sd[p + 'self_attn.k_proj.weight'] = w(shape.n_kv_heads * hd, shape.hidden)
         sd[p + 'self_attn.v_proj.weight'] = w(shape.n_kv_heads * hd, shape.hidden)
         sd[p + 'self_attn.o_proj.weight'] = w(shape.hidden, shape.n_heads * hd, out_std)
+        if getattr(shape, 'qkv_bias', False):
+            # trained Qwen2 biases are mostly small with a few large K entries (|b| of several units): draw the same kind, so that a
+            # lost or misplaced bias changes the tokens
+            for nm, n in (('q_proj', shape.n_heads * hd), ('k_proj', shape.n_kv_heads * hd), ('v_proj', shape.n_kv_heads * hd)):
+                b = torch.randn(n, generator=g, device=device, dtype=torch.float32) * 0.1
+                if nm == 'k_proj':
+                    big = torch.rand(n, generator=g, device=device) < 0.1
+                    b = torch.where(big, torch.randn(n, generator=g, device=device, dtype=torch.float32) * 4.0, b)
+                sd[p + f'self_attn.{nm}.bias'] = b.to(dtype)
         if shape.n_experts > 0:                      # HF Mixtral naming (w1 = gate, w3 = up, w2 = down)
             sd[p + 'block_sparse_moe.gate.weight'] = w(shape.n_experts, shape.hidden)
             for e in range(shape.n_experts):
@@ -202,6 +227,17 @@ def random_weights(shape, seed=0, std=0.02, device='cpu', dtype=torch.bfloat16, 
     return sd
 
 
+def check_biases(shape, state_dict):
+    """The q/k/v bias of a Qwen2 shape (shape.qkv_bias) is applied in the QKV epilogues; any other bias — Llama's attention_bias=True
+    puts one on o_proj too, mlp_bias=True on the MLP — has no kernel here and is REFUSED rather than dropped: dropping it would
+    silently compute another model."""
+    qkv = re.compile(r'\.self_attn\.[qkv]_proj\.bias$')
+    for k in (state_dict or {}):
+        if k.endswith('.bias') and not (getattr(shape, 'qkv_bias', False) and qkv.search(k)):
+            why = 'q/k/v biases need a shape with qkv_bias=True (Qwen2)' if qkv.search(k) else 'only q_proj / k_proj / v_proj biases are supported'
+            raise ValueError(f'the state dict carries {k}: {why}; refusing to drop it')
+
+
 DEFAULT_LAB = False      # engines created without lab=... take the product library; the lab_build fixture of tests/conftest.py flips it for a variant test
 
 
@@ -212,6 +248,7 @@ class LlamaVerifyEngine(object):
 
     def __init__(self, shape, state_dict, max_length=2048, device='cuda:0', attn_split=0, gemm_cfg=None,
                  consume_state_dict=False, balanced=True, n_slots=1, fuse=0, max_blocks=0, kv_ring=False, dtype=None, lab=None):
+        check_biases(shape, state_dict)
         if not torch.cuda.is_available():
             raise RuntimeError('LlamaVerifyEngine needs an MI355X: the verify step has no CPU fallback')
         # The engine computes in the checkpoint's own 16-bit type: bfloat16 (BASELINE) or float16 (what the reference's examples and
@@ -349,9 +386,20 @@ class LlamaVerifyEngine(object):
         perm_np = np.zeros(n_qkv, dtype=np.int32)
         check(self._lib.la_qkv_row_perm(shape.n_heads, shape.n_kv_heads, perm_np.ctypes.data_as(_lib.pi32)), 'qkv_row_perm')
         qkv_perm = torch.from_numpy(perm_np.astype(np.int64)).to(self.device)
+        has_bias = bool(getattr(shape, 'qkv_bias', False))
         layers = (_lib.LlamaLayerWeightsC * shape.n_layers)()
         for i in range(shape.n_layers):
             p = f'model.layers.{i}.'
+            if has_bias:
+                # one lane-ordered vector [q heads | k heads | v heads] x 128 lanes (zeros on padding lanes): the layout every QKV
+                # epilogue reads, whatever the row order of the weight image (la_gemm64_qkv_bias)
+                try:
+                    bq, bk, bv = (take(p + f'self_attn.{n}_proj.bias') for n in 'qkv')
+                except KeyError as e:
+                    raise ValueError(f'shape.qkv_bias is set but the state dict has no {e.args[0]}') from None
+                bias = torch.cat([to_lanes(b.to(self.device).reshape(-1, 1), nh_, 0).reshape(-1)
+                                  for b, nh_ in ((bq, shape.n_heads), (bk, shape.n_kv_heads), (bv, shape.n_kv_heads))])
+                layers[i].qkv_bias = dev(bias).data_ptr()
             qkv = torch.cat([to_lanes(take(p + 'self_attn.q_proj.weight').to(self.device), shape.n_heads, 0),
                              to_lanes(take(p + 'self_attn.k_proj.weight').to(self.device), shape.n_kv_heads, 0),
                              to_lanes(take(p + 'self_attn.v_proj.weight').to(self.device), shape.n_kv_heads, 0)], 0)
