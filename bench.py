@@ -20,9 +20,15 @@ says which mode a number comes from.
 
 Other workloads (secondary lines, same JSON shape; BASELINE configs 3-4): --batch B runs B sequences per GPU, each with its OWN
 64-token tree per step, in one pass over the weights (la_llama_mstep, M = 64 B rows); --model 13b|mistral picks the shape.
-The line also carries: the 8(d) fixed "T64/B8" tree with the accept sweep a in {0,3,6,12} (`fixed_tree_sweep`), the
-reference-style speed including prefill (`speed_incl_prefill`), and `cpu_baseline`: the oracle's own lookahead loop (a port of
-the reference's transformers CPU path) run on this box's host cores on the full 32-layer model for a few real verify steps.
+
+A plain run does what the headline needs and nothing else: set-up (weights, greedy continuation, trie warm-up), the W warm-up
+and K timed steps, --dump-outputs, one JSON result line.  --full adds everything else the benchmark measures, after the timed
+region: the same steps through the native loop (`native_loop`), the 8(d) fixed "T64/B8" tree with the accept sweep
+a in {0,3,6,12} (`fixed_tree_sweep`), the per-kernel roofline of the 64-row step (its own profiling passes), `cpu_baseline`
+(the oracle's own lookahead loop, a port of the reference's transformers CPU path, on the host cores, full 32-layer model, a
+few real verify steps), the `secondary` legs (other models and batch sizes, each its own `--full` process) and the
+BENCH_DETAIL record before the result line.  --no-cpu-baseline, --secondary, --secondary-multi and --profile-iters shape what
+--full adds.  Either way the line carries the reference-style speed including prefill (`speed_incl_prefill`).
 """
 import argparse
 import json
@@ -177,8 +183,8 @@ def self_launch(args_gpus, argv):
 
 
 def secondary_legs(spec, gpus=1, layers=0):
-    """The batch configurations (BASELINE configs 3-5) as secondary lines of the default run: each `model:batch` leg is this script
-    run again in its own process (`--model M --batch B`, 24 timed steps, no CPU leg) after the headline's timed region; the
+    """The batch configurations (BASELINE configs 3-5) as secondary lines of a --full run: each `model:batch` leg is this script
+    run again in its own process (`--model M --batch B --full`, 24 timed steps, no CPU leg) after the headline's timed region; the
     fields a reader needs are kept.  A leg that fails is reported as such — it never touches the headline line."""
     import subprocess
     legs = []
@@ -189,7 +195,7 @@ def secondary_legs(spec, gpus=1, layers=0):
         parts = item.split(':')
         model, batch = parts[0], parts[1]
         dev_trie_leg = len(parts) > 2 and parts[2] == 'dev'      # model:batch:dev = the same leg with the drafts from the ON-GPU trie (the default from 8 sequences on)
-        leg_args = ['--gpus', str(gpus), '--model', model, '--batch', batch, '--steps', '24', '--warmup', '4', '--no-cpu-baseline']
+        leg_args = ['--gpus', str(gpus), '--model', model, '--batch', batch, '--steps', '24', '--warmup', '4', '--no-cpu-baseline', '--full']
         if dev_trie_leg:
             leg_args.append('--device-trie')
         if len(parts) > 2 and parts[2] == 'host':                # model:batch:host = the drafts from the host trie where the default is the on-GPU trie
@@ -253,9 +259,13 @@ NOTES = {
 }
 
 
-def compact_record(out):
+PLAIN_NOTES = ('workload', 'value', 'draft_retrieval', 'trie_update')      # the notes a plain run (no --full) carries
+
+
+def compact_record(out, full=True):
     """The driver keeps the last 8 KB of stdout: the final JSON line carries the contract fields and one compact object per secondary leg;
-    prose and bulky diagnostics stay in the BENCH_DETAIL line printed before it."""
+    prose and bulky diagnostics stay in the BENCH_DETAIL line printed before it.  full=False: the line of a plain run, the only line it
+    prints, with the notes on the headline and its config (a roofline there is the batch form, priced from the timed steps alone)."""
     c, r, cpu = out['config'], out.get('roofline') or {}, out.get('cpu_baseline')
     sip = c.get('speed_incl_prefill') or {}
     cfg = {k: c.get(k) for k in ('workload', 'model', 'n_layers', 'n_layers_truncated', 'prompt_len', 'parallelism', 'sequences', 'kv_cache', 'gather_mode', 'gather_transport',
@@ -278,11 +288,11 @@ def compact_record(out):
         roof['mfma'] = {k: r['mfma'].get(k) for k in ('achieved_TFLOPs', 'frac')}
     comp = {k: out[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data')}
     comp['config'] = cfg
-    comp['roofline'] = roof
+    comp['roofline'] = roof or None
     comp['cpu_baseline'] = None if cpu is None else {k: cpu.get(k) for k in ('value', 'unit', 'cores', 'kind', 'sample', 'ms_per_step', 'mean_accept_len', 'cpu_model', 'verify_steps', 'fallback_reason') if cpu.get(k) is not None}
     if 'secondary' in out:
         comp['secondary'] = out['secondary']
-    comp['notes'] = NOTES
+    comp['notes'] = NOTES if full else {k: NOTES[k] for k in PLAIN_NOTES}
     return comp
 
 
@@ -437,8 +447,8 @@ def main():
     ap.add_argument('--copies', type=int, default=12, help='noisy copies of the continuation put into the trie')
     ap.add_argument('--layers', type=int, default=0, help='debug: override layer count (invalidates the metric)')
     ap.add_argument('--pure-random', action='store_true', help='plain N(0,0.02) init (greedy/lookahead drift apart in bf16)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-steps', type=int, default=5, help='verify steps of the CPU baseline loop')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave out the cpu_baseline leg')
+    ap.add_argument('--cpu-steps', type=int, default=5, help='--full: verify steps of the CPU baseline loop')
     ap.add_argument('--model', choices=['7b', '13b', 'mistral', 'mixtral'], default='7b',
                     help='7b = the BASELINE metric; 13b / mistral / mixtral = the config-4 / config-3 / config-5 model shapes')
     ap.add_argument('--batch', type=int, default=1, help='sequences per GPU; > 1: each gets its own 64-token tree per step (la_llama_mstep)')
@@ -456,12 +466,12 @@ def main():
                          'decoding_kwargs[\'overlap_trie_update\'] of the product loop), i.e. drafts see a step\'s tokens one step later — the split-phase '
                          'order the N > 1 job uses; emitted tokens are unaffected.  The round-5 records measured THIS order by default; the default '
                          'secondary legs carry it as mistral:8:deferred beside the reference-order line')
-    ap.add_argument('--profile-iters', type=int, default=3)
+    ap.add_argument('--profile-iters', type=int, default=3, help='--full: passes of the bs=1 per-class profile (roofline)')
     ap.add_argument('--attn-split', type=int, default=0, help='key splits of the tree-attention kernel (0 = engine default 8)')
     ap.add_argument('--fuse', type=int, default=0, help='engine cfg.fuse bits (opt-in in-kernel norm->GEMM fusion; 0 = separate kernels)')
     ap.add_argument('--gemm-cfg', default='', help='engine gemm_cfg override (comma list: qkv_rb,qkv_ks,o_rb,o_ks,down_rb,down_ks,lm_rb,gu_variant; 0 = default)')
     ap.add_argument('--secondary', default='mistral:8,mistral:8:host,mistral:8:deferred,13b:4,mixtral:4,13b:1',
-                    help='N=1 default workload only: comma list of model:batch legs (BASELINE configs 3-5: a 64-token tree per sequence '
+                    help='--full, N=1 default workload only: comma list of model:batch legs (BASELINE configs 3-5: a 64-token tree per sequence '
                          'through la_llama_mstep) run AFTER the timed region, each in its own process; their lines are embedded under '
                          '"secondary"; model:batch:dev = the same leg with the drafts from the on-GPU trie (BASELINE config 3 as stated: the host-trie line '
                          'stands beside it); 13b:1 = the 64-row step at a larger launch size (the HBM fraction rises with bytes per launch).  "" = none')
@@ -475,7 +485,7 @@ def main():
                     help='launch-path tests only: run the secondary legs too although --layers truncates the model, each with this many '
                          'layers (their lines carry n_layers; such numbers are NOT the metric)')
     ap.add_argument('--secondary-multi', default=None,
-                    help='N > 1 default workload only: model:batch legs run as their own N-rank jobs after the headline (default: '
+                    help='--full, N > 1 default workload only: model:batch legs run as their own N-rank jobs after the headline (default: '
                          '"13b:4" at --gpus 8 = BASELINE config 4, Llama-2-13B bs=32 batch-sharded over 8 GPUs; "" = none)')
     ap.add_argument('--cpu-baseline-only', action='store_true',
                     help='no GPU: time only the cpu_baseline leg (the reference itself where /root/reference is importable, else the port) on the '
@@ -483,6 +493,10 @@ def main():
     ap.add_argument('--dump-outputs', default='', metavar='DIR',
                     help='after the timed steps, write what they computed (emitted tokens; the last step\'s accepted tokens and logits) as '
                          'DIR/<name>.npy, at most 64 MB: the inputs are seeded, so two builds can be compared output for output (dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline does not need: native loop, fixed-tree sweep, per-kernel '
+                         'roofline (bs=1), CPU baseline, secondary legs; print the BENCH_DETAIL record before the result line.  Without it '
+                         'a run sets up, warms up, times its steps, dumps (--dump-outputs) and prints the result line only')
     args = ap.parse_args()
     if args.cpu_baseline_only:
         return cpu_only(args)
@@ -550,7 +564,9 @@ def main():
     # wide trees in a batch: every sequence's tree is ceil(DL / 64) blocks of the pass (eng.mstep_trees), all of them within the 8-block pass
     assert not wide or B == 1 or (B * ((DL + 63) // 64) <= 8 and not args.device_trie and world == 1), \
         'wide trees with --batch B: B x ceil(decoding_length / 64) <= 8 blocks, host trie, one GPU'
-    n_truth = (K + W + 56) * (BL + 1) + 8          # measured steps + native-loop leg (16 steps) + fixed-tree sweep (24 steps) + slack
+    # measured steps + native-loop leg (16 steps) + fixed-tree sweep (24 steps) + slack; the same length without --full: the trie
+    # warm-up's noisy copies are drawn over the whole continuation, so a shorter one would change the drafts of the timed steps
+    n_truth = (K + W + 56) * (BL + 1) + 8
     max_length = P + n_truth + 2 * DL
     # Mistral (config 2): the checkpoint's sliding window (4096, HF Mistral-7B-v0.1 config.json) with the KV cache as a ring of
     # window + one step of rows per sequence (memory O(window), not O(max_length)); contexts of this workload stay inside the window
@@ -559,7 +575,7 @@ def main():
     kv_ring = bool(getattr(shape, 'sliding_window', 0)) and B > 1
     if kv_ring:
         max_length = max(max_length, shape.sliding_window + 64 * B * ((DL + 63) // 64) + 64)
-    want_cpu = not args.no_cpu_baseline and world == 1 and B == 1      # the CPU leg is timed on rank 0 at N=1 only
+    want_cpu = args.full and not args.no_cpu_baseline and world == 1 and B == 1      # the CPU leg is timed on rank 0 at N=1 only
     tdtype = torch.float16 if args.dtype == 'fp16' else torch.bfloat16
     sd = random_weights(shape, seed=0, device=dev, decisive=not args.pure_random, dtype=tdtype)
     sd_cpu = {k: v.cpu() for k, v in sd.items()} if want_cpu else None
@@ -800,7 +816,7 @@ def main():
     if args.dump_outputs:                # before the legs below run more steps on the engine
         dump_outputs(args.dump_outputs, eng, seqs, P, dls[-B:], edls[-B:], wide, rank, world)
     native = None
-    if B == 1 and not wide and not dist_on and len(seqs[0]) + (BL + 1) * (16 + 24) < max_length - 2 * DL:
+    if args.full and B == 1 and not wide and not dist_on and len(seqs[0]) + (BL + 1) * (16 + 24) < max_length - 2 * DL:
         # informational: the same steps through the native loop (la_lookahead_decode, what lookahead_generation() uses when
         # no streamer / processor is attached).  `value` stays on the interpreter loop, which is also what N > 1 runs.
         torch.cuda.synchronize()
@@ -815,7 +831,7 @@ def main():
 
     # ---- 8(d) fixed draft-tree shape "T64/B8" with the accept sweep: the main chain equals the greedy continuation for a tokens
     sweep = None
-    if B == 1 and not wide and not dist_on and not args.pure_random:
+    if args.full and B == 1 and not wide and not dist_on and not args.pure_random:
         parent, depth, rows64 = fixed_t64b8_tree()
         truth = truths[gidx[0]]
         sweep = {}
@@ -857,7 +873,8 @@ def main():
     mean_T = float(np.mean(dls[n0:]))
     mean_acc = float(np.mean(edls[n0:]))
     W_bytes = 2 * shape.n_params_no_embed()
-    if B == 1 and not wide:
+    roofline = None                      # bs=1 without --full: the profiling passes below are runs of their own
+    if args.full and B == 1 and not wide:
         # dominant kernel (gate/up GEMM, k_gemm64r<4,SWIGLU,4,8>) from live HIP events on the engine's stream
         ids, rowmask = drafts_for(0)
         prof = eng.profile(ids, rowmask, iters=args.profile_iters)
@@ -907,7 +924,7 @@ def main():
                             'ms_by_class_events': {k: round(v, 4) for k, v in prof['ms'].items()},
                             'all_gemm_GBps_events': round(2 * shape.n_params_no_embed() / (gemm_ms * 1e-3) / 1e9, 1)},
         }
-    else:
+    elif B > 1 or wide:
         # M = 64 B rows per step: near / past the ridge -> the step is priced against BOTH roofs from its wall time;
         # per-kernel durations of the same step: profiles/r02_mblock_kernel_stats_*.txt (rocprofv3 --kernel-trace --stats)
         kv_tok = 2 * shape.n_layers * shape.n_kv_heads * shape.head_dim * 2
@@ -944,7 +961,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     secondary = None
-    sec_ok = (not args.layers) or args.secondary_layers > 0
+    sec_ok = args.full and ((not args.layers) or args.secondary_layers > 0)
     if world == 1 and B == 1 and args.model == '7b' and sec_ok and args.secondary and not os.environ.get('BENCH_IS_SECONDARY'):
         secondary = secondary_legs(args.secondary, layers=args.secondary_layers)
     multi = secondary_multi_spec(args.secondary_multi, world)
@@ -988,6 +1005,9 @@ def main():
     }
     if secondary is not None:
         out['secondary'] = secondary
+    if not args.full:                    # a plain run: the result line is all it prints
+        print(json.dumps(compact_record(out, full=False)), flush=True)
+        return
     # the full record first (not the last line), then the compact contract line the driver parses and whose tail it keeps
     detail = json.dumps(out)
     print('BENCH_DETAIL ' + detail, flush=True)

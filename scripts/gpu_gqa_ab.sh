@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_gpu_mblock.py tests/test_gpu_kernels.py 
 for leg in "mistral 8" "mixtral 4" "mistral 1"; do
   set -- $leg
   for i in 1 2; do
-    timeout 300 python bench.py --model $1 --batch $2 --steps 24 --warmup 4 --no-cpu-baseline --secondary "" 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --model $1 --batch $2 --steps 24 --warmup 4 --no-cpu-baseline --secondary "" 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -98,7 +98,7 @@ def test_self_launch_command_and_clean_environment(monkeypatch):
 
 
 def test_eight_rank_run_adds_config4_as_its_own_job_by_default():
-    """`python bench.py --gpus 8` (the driver's scaling run) follows the headline with BASELINE config 4 — Llama-2-13B, 4 sequences per
+    """`python bench.py --gpus 8 --full` follows the headline with BASELINE config 4 — Llama-2-13B, 4 sequences per
     GPU = bs 32 over the 8 ranks — as its own 8-rank job; other rank counts add none unless --secondary-multi names legs."""
     assert bench.secondary_multi_spec(None, 8) == '13b:4'
     assert bench.secondary_multi_spec(None, 2) == '' and bench.secondary_multi_spec(None, 4) == ''
@@ -275,3 +275,52 @@ def test_compact_record_keeps_the_contract_fields_and_fits_the_drivers_captured_
     assert len(comp['secondary']) == 6 and all(leg['traffic_ratio'] == round(28400000000 / 14970000000, 3) and leg['equals_greedy'] is True for leg in comp['secondary'])
     assert [leg['draft_retrieval'] for leg in comp['secondary'][:2]] == ['host', 'device'] and comp['secondary'][0]['model'] == 'Mistral-7B'
     assert comp['config']['workload'].startswith('Llama-2-7B') and 'workload' in comp['notes']
+
+
+def test_plain_record_keeps_the_contract_fields_and_the_headline_notes():
+    """A run without --full prints bench.compact_record(out, full=False) and nothing else: the contract fields as a --full run states
+    them, no bs=1 roofline (its profile passes are runs of their own), no CPU leg, no legs, and the notes on the headline and its
+    config; a batch run keeps its roofline, priced from the timed steps alone."""
+    import json
+    cfg = {'workload': 'Llama-2-7B bf16 bs=1/GPU lookahead verify loop', 'model': 'Llama-2-7B', 'n_layers': 32, 'sequences': 1, 'mean_accept_len': 6.45,
+           'mean_draft_len': 53.55, 'lookahead_equals_greedy': True, 'native_loop': None, 'fixed_tree_sweep': None,
+           'speed_incl_prefill': {'prefill_ms': 10.4, 'tokens_per_sec': 1518.5, 'at_256_new_tokens': 1616.8, 'note': 'n'}}
+    out = {'metric': 'accepted_tokens_per_sec', 'value': 1730.68, 'unit': 'tokens/s', 'n_gpus': 1, 'steps': 20, 'warmup': 5, 'ms_per_step': 3.7269,
+           'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic', 'config': cfg,
+           'roofline': None, 'cpu_baseline': None}
+    comp = bench.compact_record(out, full=False)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup'):
+        assert comp[k] == out[k], k
+    assert comp['roofline'] is None and comp['cpu_baseline'] is None and 'secondary' not in comp and 'native_loop' not in comp['config']
+    assert set(comp['notes']) == set(bench.PLAIN_NOTES) and all(comp['notes'][k] == bench.NOTES[k] for k in comp['notes'])
+    assert len(json.dumps(comp)) < 8000
+    roof = {'bound': 'mfma', 'achieved': 776.1, 'peak': 2500.0, 'unit': 'TFLOP/s', 'frac': 0.31, 'traffic': None,
+            'hbm': {'algorithmic_bytes': 14970000000, 'achieved_GBps': 1555.0, 'frac': 0.194}, 'mfma': {'flops': 7.46e12, 'achieved_TFLOPs': 776.1, 'frac': 0.31}}
+    comp_b = bench.compact_record(dict(out, roofline=roof, config=dict(cfg, sequences=8)), full=False)
+    assert comp_b['roofline']['bound'] == 'mfma' and comp_b['roofline']['hbm']['frac'] == 0.194
+    assert set(comp_b['notes']) == set(bench.PLAIN_NOTES)
+    assert bench.compact_record(dict(out, roofline=roof))['notes'] == bench.NOTES          # --full: every note, as before
+
+
+def test_secondary_legs_run_as_full_processes(monkeypatch):
+    """--full runs each secondary leg as `bench.py ... --full` (their own roofline, native-loop and sweep figures where they have them);
+    a leg that fails is reported with its error and the others still run."""
+    import subprocess
+    import sys
+
+    seen = []
+
+    class Done(object):
+        returncode, stdout, stderr = 1, '', 'stub: no GPU'
+
+    def fake_run(cmd, **kw):
+        seen.append((cmd, kw['env']))
+        return Done()
+    monkeypatch.setattr(subprocess, 'run', fake_run)
+    legs = bench.secondary_legs('mistral:8,mistral:8:host,13b:1')
+    assert [leg['model'] for leg in legs] == ['mistral', 'mistral', '13b'] and all('stub: no GPU' in leg['error'] for leg in legs)
+    assert len(seen) == 3
+    for cmd, env in seen:
+        assert cmd[0] == sys.executable and cmd[1].endswith('bench.py') and '--full' in cmd and '--no-cpu-baseline' in cmd
+        assert env['BENCH_IS_SECONDARY'] == '1'
+    assert '--host-trie' in seen[1][0] and cmd[cmd.index('--model') + 1] == '13b' and cmd[cmd.index('--batch') + 1] == '1'

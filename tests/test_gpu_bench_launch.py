@@ -21,7 +21,7 @@ def test_bench_self_launches_two_ranks(strict):
         env.pop(k, None)
     env.update({'BENCH_SHARE_GPU': '1', 'BENCH_DIST_BACKEND': 'gloo'})
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2', '--layers', '2',
-           '--no-cpu-baseline', '--secondary', ''] + (['--strict-gather'] if strict else [])
+           '--no-cpu-baseline', '--secondary', '', '--full'] + (['--strict-gather'] if strict else [])
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1000:], r.stderr[-3000:])
@@ -62,7 +62,7 @@ def test_bench_gathers_over_rccl_with_one_rank_per_gpu():
 
 @pytest.mark.gpu
 def test_bench_self_launches_two_ranks_and_runs_config4_as_its_own_multi_rank_job():
-    """`python bench.py --gpus N` as the driver's scaling run calls it (no rank environment): N ranks of the headline workload, then
+    """`python bench.py --gpus N --full` with no rank environment: N ranks of the headline workload, then
     BASELINE config 4 — Llama-2-13B, 4 sequences per GPU, batch-sharded over the N ranks — as its own N-rank job embedded under
     `secondary` (at --gpus 8 that leg is the default, tests/test_bench_helpers_cpu.py).  The box has one GPU, which at most a handful
     of processes may hold open at once: N = 2 ranks share it (the first job's ranks, the second job's ranks and this process overlap
@@ -73,7 +73,7 @@ def test_bench_self_launches_two_ranks_and_runs_config4_as_its_own_multi_rank_jo
         env.pop(k, None)
     env.update({'BENCH_SHARE_GPU': '1', 'BENCH_DIST_BACKEND': 'gloo'})
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--layers', '2',
-           '--secondary-layers', '2', '--secondary-multi', '13b:4', '--no-cpu-baseline', '--strict-gather']
+           '--secondary-layers', '2', '--secondary-multi', '13b:4', '--no-cpu-baseline', '--strict-gather', '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1000:], r.stderr[-3000:])
@@ -120,3 +120,35 @@ def test_bench_dump_outputs_hold_the_last_timed_step_and_repeat_run_to_run(tmp_p
         assert n_last >= 1 and np.array_equal(gen[i, n_gen - n_last:n_gen], last[i, :n_last])     # the last step's tokens end the sequence
         root = [k for k in range(rows.shape[0]) if rows[k, 0] == i and rows[k, 1] == 0]
         assert len(root) == 1 and int(np.argmax(lg[root[0]])) == int(last[i, 0])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone_and_full_adds_the_rest_on_the_same_timed_steps(tmp_path):
+    """Without --full a run prints one line (no BENCH_DETAIL record) and measures nothing beyond its timed steps: no native-loop
+    or fixed-tree legs, no bs=1 roofline profile, no CPU leg, no secondary legs.  --full adds them after the timed region, so the
+    timed steps of both runs compute the same: equal dumps, accept lengths and headline fields."""
+    def run(out_dir, *extra):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--layers', '2',
+               '--dump-outputs', str(out_dir)] + list(extra)
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith(('{', 'BENCH_DETAIL'))]      # (the runtime may print notices)
+        assert out and out[-1].startswith('{"metric"') and sum(ln.startswith('{"metric"') for ln in out) == 1, out
+        names = ('generated_tokens', 'last_step_tokens', 'last_step_logits', 'last_step_logit_rows')
+        return out, json.loads(out[-1]), {n: np.load(os.path.join(out_dir, n + '.npy')) for n in names}
+    out_p, plain, dump_p = run(tmp_path / 'plain')
+    assert len(out_p) == 1, out_p                                # no BENCH_DETAIL record
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in plain
+    assert plain['steps'] == 3 and plain['warmup'] == 1 and plain['config']['lookahead_equals_greedy'] is True
+    assert plain['roofline'] is None and plain['cpu_baseline'] is None and 'secondary' not in plain
+    assert 'native_loop' not in plain['config'] and 'detail' not in plain['notes'] and 'workload' in plain['notes']
+    out_f, full, dump_f = run(tmp_path / 'full', '--full', '--no-cpu-baseline', '--secondary', '')
+    assert any(ln.startswith('BENCH_DETAIL {') for ln in out_f)
+    assert full['roofline']['verify_step']['ms_graph_step'] > 0 and full['config']['native_loop']['equals_greedy'] is True
+    detail = json.loads([ln for ln in out_f if ln.startswith('BENCH_DETAIL {')][0][len('BENCH_DETAIL '):])
+    assert all(v['accepted_as_designed'] for v in detail['config']['fixed_tree_sweep'].values())
+    for k in ('mean_accept_len', 'mean_draft_len', 'context_mean_timed', 'context_at_end', 'lookahead_equals_greedy'):
+        assert plain['config'][k] == full['config'][k], k
+    for n in dump_p:
+        assert np.array_equal(dump_p[n], dump_f[n]), n
