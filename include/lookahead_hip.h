@@ -43,7 +43,7 @@ extern "C" {
 #define LA_MOE_MAX_E      8   /* experts per mixture-of-experts layer (Mixtral: 8, top-2) */
 
 /* ABI version: bumped when a signature changes. */
-#define LA_ABI_VERSION  13   /* bumped whenever a struct layout or an entry point changes */
+#define LA_ABI_VERSION  14   /* bumped whenever a struct layout or an entry point changes */
 int          la_abi_version(void);   /* == LA_ABI_VERSION of the header the library was built from */
 /* Storage / MFMA-input type of the loaded library: 0 = bfloat16 (liblookahead_hip.so), 1 = float16 (liblookahead_hip_f16.so, the
  * dtype the reference's examples and benchmarks run, lookahead/benchmarks/llama_benchmark.py:27).  The two libraries are the same
@@ -348,6 +348,27 @@ int la_gemm64r_qkv_bias(void* stream, const void* d_wp, const void* d_xp, int n_
                         void* d_qf, void* d_kfresh, void* d_vfresh, const void* d_bias);
 int la_gemm64_logits(void* stream, const void* d_wp, const void* d_xp, int V, int K, int rb,
                      void* d_logits_bf16 /*[64][V] or NULL*/, float* d_cand_val, int32_t* d_cand_idx);
+/* FP8 weight-only (W8A16) forms.  The weights are OCP e4m3fn bytes, W'[n][k] = s[n] * q[n][k], one fp32 scale per output row
+ * (d_scale, 16-byte aligned); activations, accumulation and every rounding point stay those of the 16-bit entry points, and
+ * s[n] is multiplied in once, in fp32, after the K reduction (before the q/k/v bias).  The packers take [N][K] e4m3fn bytes and
+ * write the 16-bit layouts with 1-byte elements (la_planned_elems then counts bytes).  Scale vectors: QKV lane-ordered like the
+ * bias, [(nh + 2 nkv) * 128] at slot * 128 + lane (padding lanes 1) whatever the row order of the image; gate/up [2][F] (gate
+ * rows, then up rows); slab [N].  Forms: slab rb = 2 | 0 << 8 or 2 | 3 << 8 (N % 64 == 0); swiglu / qkv variant 0. */
+int la_pack_weight_fp8(void* stream, const void* d_w, const void* d_w2, int N, int K, int interleave2, void* d_out);
+int la_pack_planned_fp8(void* stream, const void* d_w, const void* d_w2, const int32_t* d_plan, int kind, int n_rows, int K,
+                        int n_wg, void* d_out);
+int la_gemm64_slab_fp8(void* stream, const void* d_wp, const void* d_xp, int N, int K, int rb, int ksplit, float* d_slabs,
+                       const float* d_scale);
+int la_gemm64_swiglu_fp8(void* stream, const void* d_wp_gateup, const void* d_xp, int F, int K, void* d_act_packed,
+                         const float* d_scale);
+int la_gemm64_qkv_fp8(void* stream, const void* d_wp, const void* d_xp, int n_heads, int n_kv_heads, int K,
+                      const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
+                      void* d_qf, void* d_kfresh, void* d_vfresh, const void* d_bias /*or NULL*/, const float* d_scale);
+int la_gemm64r_swiglu_fp8(void* stream, const void* d_wp, const void* d_xp, int F, int K, int n_wg, void* d_act_packed,
+                          const float* d_scale);
+int la_gemm64r_qkv_fp8(void* stream, const void* d_wp, const void* d_xp, int n_heads, int n_kv_heads, int K, int n_wg,
+                       const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
+                       void* d_qf, void* d_kfresh, void* d_vfresh, const void* d_bias /*or NULL*/, const float* d_scale);
 int la_argmax_finalize(void* stream, const float* d_cand_val, const int32_t* d_cand_idx, int n_tiles,
                        int32_t* d_state);
 
@@ -407,6 +428,10 @@ typedef struct la_llama_config {
                                 (HBM streaming); at 192-512 rows the launch is MFMA-bound and a GQA model's 24 rows per workgroup
                                 (12 RoPE pairs in a 32-row MFMA block) waste 5/8 of the matrix-core work: fewer, fuller workgroups
                                 (Mistral: 96 x 32 pairs) x token quarters instead */
+    int32_t weight_format;   /* 0 = q/k/v, o, gate/up and down images in the storage type; 1 = fp8 e4m3fn images (la_pack_weight_fp8 /
+                                la_pack_planned_fp8) with per-row fp32 scales (la_llama_layer_weights.*_scale).  Embedding, norms,
+                                bias, lm_head and the KV cache stay 16-bit.  1 needs n_experts = 0, max_blocks <= 1, fuse = 0, the
+                                fused QKV image and the default GEMM plan (o / down rb 2, variants 0 or 3; qkv / gate/up variant 0) */
 } la_llama_config;
 
 typedef struct la_llama_layer_weights {   /* device pointers, packed by la_pack_weight */
@@ -425,6 +450,11 @@ typedef struct la_llama_layer_weights {   /* device pointers, packed by la_pack_
     const void* wqkv_mb;             /* cfg.qkv_mb_wg > 0: the QKV rows once more, planned for cfg.qkv_mb_wg workgroups (multi-block step) */
     const void* qkv_bias;            /* NULL = no bias (Llama, Mistral, Mixtral); Qwen2: the lane-ordered q/k/v bias of la_gemm64_qkv_bias,
                                         [(nh+2*nkv)*128] in the storage type, 8-byte aligned — every step entry point adds it in its QKV launch */
+    /* weight_format 1: fp32 per-row scales of the fp8 images, 16-byte aligned (layouts: la_gemm64_slab_fp8 and its kin) */
+    const float* wqkv_scale;         /* lane-ordered [(nh+2*nkv)*128] */
+    const float* wo_scale;           /* [hidden] */
+    const float* wgateup_scale;      /* [2][ffn] */
+    const float* wdown_scale;        /* [hidden] */
 } la_llama_layer_weights;
 
 typedef struct la_llama_weights {

@@ -19,7 +19,7 @@ LIB_PATH_F16 = LAB_PATH_F16 if LAB_BUILD else os.path.join(_HERE, "liblookahead_
 LA_DTYPE_BF16, LA_DTYPE_F16 = 0, 1
 
 LA_OK = 0
-ABI_VERSION = 13        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
+ABI_VERSION = 14        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
 LA_MODE_INPUT, LA_MODE_OUTPUT, LA_MODE_MIX = 0, 1, 2
 LA_TREE_MAX = 64
 LA_MOE_MAX_E = 8
@@ -86,13 +86,13 @@ class LlamaConfigC(C.Structure):
                 ("ffn", i32), ("vocab", i32), ("max_keys", i32), ("max_pos", i32), ("attn_split", i32),
                 ("rms_eps", f32), ("gemm_cfg", i32 * 8), ("balanced_wg", i32 * 3), ("n_slots", i32),
                 ("n_experts", i32), ("top_k", i32), ("fuse", i32), ("sliding_window", i32), ("kv_ring", i32), ("max_blocks", i32),
-                ("norm_cast_first", i32), ("qkv_mb_wg", i32)]
+                ("norm_cast_first", i32), ("qkv_mb_wg", i32), ("weight_format", i32)]
 
 
 class LlamaLayerWeightsC(C.Structure):
     _fields_ = [("wqkv", vp), ("wo", vp), ("wgateup", vp), ("wdown", vp), ("norm1", vp), ("norm2", vp),
                 ("router", vp), ("ex_gateup", C.POINTER(vp)), ("ex_down", C.POINTER(vp)), ("wqkv_mb", vp),
-                ("qkv_bias", vp)]
+                ("qkv_bias", vp), ("wqkv_scale", vp), ("wo_scale", vp), ("wgateup_scale", vp), ("wdown_scale", vp)]
 
 
 class LlamaWeightsC(C.Structure):
@@ -181,6 +181,13 @@ PROTOTYPES = {
     "la_gemm64r_qkv": (i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp),
     "la_gemm64r_qkv_bias": (i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp),
     "la_gemm64_logits": (i32, vp, vp, vp, i32, i32, i32, vp, vp, vp),
+    "la_pack_weight_fp8": (i32, vp, vp, vp, i32, i32, i32, vp),
+    "la_pack_planned_fp8": (i32, vp, vp, vp, vp, i32, i32, i32, i32, vp),
+    "la_gemm64_slab_fp8": (i32, vp, vp, vp, i32, i32, i32, i32, vp, vp),
+    "la_gemm64_swiglu_fp8": (i32, vp, vp, vp, i32, i32, vp, vp),
+    "la_gemm64_qkv_fp8": (i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
+    "la_gemm64r_swiglu_fp8": (i32, vp, vp, vp, i32, i32, i32, vp, vp),
+    "la_gemm64r_qkv_fp8": (i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp),
     "la_argmax_finalize": (i32, vp, vp, vp, i32, vp),
     "la_embed_norm": (i32, vp, vp, vp, vp, i32, f32, vp, vp),
     "la_resid_norm": (i32, vp, vp, vp, i32, vp, i32, f32, vp),

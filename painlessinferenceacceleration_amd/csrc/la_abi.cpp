@@ -135,6 +135,45 @@ int la_gemm64r_qkv(void* stream, const void* wp, const void* xp, int nh, int nkv
                    const void* rcos, const void* rsin, void* qf, void* kf, void* vf) {
     return la_gemm64r_qkv_bias(stream, wp, xp, nh, nkv, K, n_wg, pos, rcos, rsin, qf, kf, vf, nullptr);
 }
+// ---- fp8 (e4m3fn) weight images + per-row fp32 scales (weight_format 1; layouts: la_common.h, WP8 / planned-8)
+static bool scale_ok(const float* s) { return s && ((uintptr_t)s & 15) == 0; }
+int la_pack_weight_fp8(void* stream, const void* w, const void* w2, int N, int K, int interleave2, void* out) {
+    if (!w || !out || N % 32 || K % 16 || (interleave2 && !w2)) return LA_E_ARG;
+    WRAP(lk_pack_weight8((hipStream_t)stream, w, w2, N, K, interleave2, out));
+}
+int la_pack_planned_fp8(void* stream, const void* w, const void* w2, const int32_t* d_plan, int kind, int n_rows, int K, int n_wg,
+                        void* out) {
+    if (!w || !d_plan || !out || kind < 0 || kind > 2 || (kind == 1 && !w2) || K % 16 || n_wg <= 0) return LA_E_ARG;
+    if (lk_rowplan(kind, n_rows, n_wg, nullptr) < 0) return LA_E_RANGE;
+    WRAP(lk_pack_planned((hipStream_t)stream, w, w2, d_plan, kind, n_rows, K, n_wg, out, 1));
+}
+int la_gemm64_slab_fp8(void* stream, const void* wp, const void* xp, int N, int K, int rb, int ksplit, float* slabs, const float* d_scale) {
+    if (!wp || !xp || !slabs || !scale_ok(d_scale) || N % 64 || K % 16 || ksplit < 1 || ksplit > 16 || (rb & 0xff) != 2 ||
+        ((rb >> 8) != 0 && (rb >> 8) != 3)) return LA_E_ARG;
+    WRAP(lk_gemm64_slab((hipStream_t)stream, wp, xp, N, K, rb, ksplit, slabs, nullptr, d_scale));
+}
+int la_gemm64_swiglu_fp8(void* stream, const void* wp, const void* xp, int F, int K, void* act, const float* d_scale) {
+    if (!wp || !xp || !act || !scale_ok(d_scale) || F % 32 || K % 16) return LA_E_ARG;
+    WRAP(lk_gemm64_swiglu((hipStream_t)stream, wp, xp, F, K, act, 0, nullptr, d_scale));
+}
+int la_gemm64_qkv_fp8(void* stream, const void* wp, const void* xp, int nh, int nkv, int K, const int32_t* pos, const void* rcos,
+                      const void* rsin, void* qf, void* kf, void* vf, const void* d_bias, const float* d_scale) {
+    if (!wp || !xp || !pos || !rcos || !rsin || !qf || !kf || !vf || nh <= 0 || nkv <= 0 || K % 16 || !bias_ok(d_bias) ||
+        !scale_ok(d_scale)) return LA_E_ARG;
+    WRAP(lk_gemm64_qkv((hipStream_t)stream, wp, xp, nh, nkv, K, pos, rcos, rsin, qf, kf, vf, 0, d_bias, d_scale));
+}
+int la_gemm64r_swiglu_fp8(void* stream, const void* wp, const void* xp, int F, int K, int n_wg, void* act, const float* d_scale) {
+    if (!wp || !xp || !act || !scale_ok(d_scale) || K % 16 || n_wg <= 0) return LA_E_ARG;
+    if (lk_gemm64r_init() != 0) return LA_E_HIP;
+    WRAP(lk_gemm64r_swiglu((hipStream_t)stream, wp, xp, F, K, n_wg, act, nullptr, nullptr, nullptr, d_scale));
+}
+int la_gemm64r_qkv_fp8(void* stream, const void* wp, const void* xp, int nh, int nkv, int K, int n_wg, const int32_t* pos,
+                       const void* rcos, const void* rsin, void* qf, void* kf, void* vf, const void* d_bias, const float* d_scale) {
+    if (!wp || !xp || !pos || !rcos || !rsin || !qf || !kf || !vf || nh <= 0 || nkv <= 0 || K % 16 || n_wg <= 0 || !bias_ok(d_bias) ||
+        !scale_ok(d_scale)) return LA_E_ARG;
+    if (lk_gemm64r_init() != 0) return LA_E_HIP;
+    WRAP(lk_gemm64r_qkv((hipStream_t)stream, wp, xp, nh, nkv, K, n_wg, pos, rcos, rsin, qf, kf, vf, nullptr, d_bias, d_scale));
+}
 int la_gemm64_logits(void* stream, const void* wp, const void* xp, int V, int K, int rb, void* logits, float* cv,
                      int32_t* ci) {
     if (!wp || !xp || !cv || !ci || V % 32 || K % 16 || ((rb & 0xff) != 1 && (rb & 0xff) != 2)) return LA_E_ARG;

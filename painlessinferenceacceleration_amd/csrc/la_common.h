@@ -14,6 +14,13 @@
 //                                 inside: lane = (d%32) + 32*hh, e, where key%32 = 16*s2 + (e&3) + 8*(e>>2) + 4*hh
 //      (the key order in which the S^T accumulator registers of the QK MFMA already sit, so P needs
 //       no cross-lane movement before the PV MFMA).
+//  WP8 / planned-8  fp8 weight images (weight_format 1: OCP e4m3fn, W'[n][k] = s[n] * q[n][k]): the SAME fragment order as WP and
+//      as the planned image with 1-byte elements — a tile is 512 bytes, a lane's fragment of one k-tile is 8 bytes (one dwordx2
+//      load), and every offset the 16-bit kernels compute in 16-byte units is the same number in 8-byte units.  So a wave streams
+//      exactly the k-tiles of the 16-bit kernel in the same order, and converts each fragment in registers (w8_frag) before the
+//      unchanged MFMA.  Scales are fp32, one per output row, multiplied in once after the cross-wave reduction:
+//        QKV     lane-ordered like qkv_bias: s[(nh + 2 nkv) * 128] at slot * 128 + lane (padding lanes 1), whatever the row order;
+//        gate/up s[2][ffn] (gate rows, then up rows);   o_proj / down_proj s[N].
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,6 +87,29 @@ __device__ __forceinline__ void qkv_bias_add(const bf16_t* __restrict__ bias, in
         if constexpr (std::is_arithmetic<V>::value) v += bf2f(bias[i]);      // a scalar site
         else v[o] += bf2f(bias[i]);
     }
+}
+// One lane's fp8 (e4m3fn) weight fragment of a k-tile (8 bytes, byte e = element e) -> the 16-bit A operand of LA_MFMA.  Every
+// e4m3 value, subnormals included, is exact in bf16 and in fp16; v_cvt_scalef32_pk_{bf16,f16}_fp8 converts two bytes per
+// instruction, with a unit scale (the per-row scale is applied in fp32 in the epilogue).  Four conversions per fragment, and each
+// fragment feeds two MFMAs.
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+__device__ __forceinline__ bf16x8 w8_frag(u32x2 q) {
+#if LA_DTYPE == 1
+    const auto c0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(q[0], 1.0f, false), c1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(q[0], 1.0f, true);
+    const auto c2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(q[1], 1.0f, false), c3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(q[1], 1.0f, true);
+#else
+    const auto c0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[0], 1.0f, false), c1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[0], 1.0f, true);
+    const auto c2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[1], 1.0f, false), c3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(q[1], 1.0f, true);
+#endif
+    const u32x4 w = {__builtin_bit_cast(unsigned, c0), __builtin_bit_cast(unsigned, c1), __builtin_bit_cast(unsigned, c2),
+                     __builtin_bit_cast(unsigned, c3)};
+    return __builtin_bit_cast(bf16x8, w);
+}
+// the A operand of a weight fragment: 16-bit images pass through untouched (the same SSA value as before), fp8 ones convert
+template <bool W8, typename T>
+__device__ __forceinline__ bf16x8 wfrag(const T& v) {
+    if constexpr (W8) return w8_frag(v);
+    else return v;
 }
 // the 32x32x16 MFMA of the build's storage type (identical operand layouts): LA_MFMA(a, b, c, 0, 0, 0)
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;

@@ -254,8 +254,25 @@ static size_t carve(la_llama* m, char* base) {
     return align_up(cv.off, 256);
 }
 
+// weight_format 1 (fp8 e4m3fn images + per-row scales): only the launches of the default single-sequence plan have fp8 forms;
+// everything else is refused here rather than run a 16-bit kernel over 1-byte weights.  Null: supported.
+static const char* w8_refusal(const la_llama_config* c) {
+    if (c->weight_format == 0) return nullptr;
+    if (c->weight_format != 1) return "weight_format: 0 (storage type) or 1 (fp8 e4m3fn + per-row scales)";
+    if (c->n_experts > 0) return "weight_format 1: MoE experts have no fp8 launch";
+    if (c->max_blocks > 1) return "weight_format 1: the multi-block step (max_blocks > 1) has no fp8 launch";
+    if (c->fuse != 0) return "weight_format 1: the fused norm / role-fused launches (fuse != 0) have no fp8 form";
+    if (c->gemm_cfg[1] < 0) return "weight_format 1: the unfused QKV (gemm_cfg[1] < 0) has no fp8 launch";
+    auto slab_ok = [](int v) { return v == 0 || v == 2 || v == (2 | (3 << 8)); };
+    if ((c->gemm_cfg[0] >> 8) != 0 || !slab_ok(c->gemm_cfg[2]) || !slab_ok(c->gemm_cfg[4]) || c->gemm_cfg[7] != 0)
+        return "weight_format 1: only the default GEMM plan has fp8 launches (gemm_cfg: qkv / gate-up variant 0, o / down rb 2 variant 0 or 3)";
+    if (c->hidden % 64) return "weight_format 1: hidden must be a multiple of 64 (two row-blocks per o / down workgroup)";
+    return nullptr;
+}
+
 static int validate(const la_llama_config* c) {
     if (!c) return LA_E_ARG;
+    if (const char* why = w8_refusal(c)) { la_set_error(why); return LA_E_ARG; }
     if (c->head_dim < 8 || c->head_dim > 128 || (c->head_dim & 1)) { la_set_error("head_dim must be even, 8 .. 128 (heads narrower than 128 run in padded 128-feature lanes)"); return LA_E_ARG; }
     if (lk_qk_scale_check(c->head_dim) != 0) { la_set_error("softmax scale: x * fp32(1 / sqrt(head_dim)) is not the rounded quotient for every bf16 x at this head_dim"); return LA_E_ARG; }
     if (c->n_layers <= 0 || c->hidden % 32 || c->hidden > 8192 || c->ffn % 32 || c->vocab % 32 ||
@@ -300,6 +317,12 @@ extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_
     m->w.layers = m->layers.data();
     for (int l = 0; l < cfg->n_layers; ++l)
         if ((uintptr_t)w->layers[l].qkv_bias & 7) { la_set_error("qkv_bias must be 8-byte aligned"); delete m; return nullptr; }
+    if (cfg->weight_format == 1)
+        for (int l = 0; l < cfg->n_layers; ++l) {
+            const la_llama_layer_weights& L = w->layers[l];
+            for (const float* sc : {L.wqkv_scale, L.wo_scale, L.wgateup_scale, L.wdown_scale})
+                if (!sc || ((uintptr_t)sc & 15)) { la_set_error("weight_format 1: every layer needs its four scale vectors, 16-byte aligned"); delete m; return nullptr; }
+        }
     if (cfg->n_experts > 0) {
         for (int l = 0; l < cfg->n_layers; ++l) {
             const la_llama_layer_weights& L = w->layers[l];
@@ -393,6 +416,10 @@ struct Prof {
 static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = false, const int32_t* zc_in = nullptr,
                         int32_t* zc_out = nullptr, int bsplit = 0, bool long_ctx = false, bool fork = false) {
     const la_llama_config& c = m->cfg;
+    // fp8 images: every prefetch descriptor (lk_pf_planned / lk_pf_classic) counts 16-bit bytes and would read past an fp8 image, and
+    // the lab's o_proj forms read 16-bit weights: all of them stay off, whatever the lab knobs say
+    const bool w8 = c.weight_format == 1;
+    if (w8) fork = false;
     // Forked weight prefetch: `fork_pf(d)` makes the side stream wait for everything queued on `st` so far and launches the
     // prefetch workgroups of descriptor d there — under stream capture a parallel branch of the graph that starts when the step
     // reaches this point and is joined at the end of the step only (nothing waits for a prefetch: it writes nothing).
@@ -426,7 +453,7 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
     if (m->fuse) HIPCHK(hipMemsetAsync(m->fuse_cnt, 0, sizeof(int) * 3 * c.n_layers, st));
     // Idle-window weight prefetch (la_kernels.h, PfDesc): the row kernels and the attention combine carry extra workgroups that
     // pull the first KiB every workgroup of the NEXT GEMM will stream into the L2 of its XCD.  g_la_pf_kib = 0 switches it off.
-    const int pf_kib = m->fuse ? 0 : g_la_pf_kib, pf_dly = g_la_pf_delay;
+    const int pf_kib = (m->fuse || w8) ? 0 : g_la_pf_kib, pf_dly = g_la_pf_delay;
     // four workgroups per norm row (k_row_norm4): single-sequence step with the fused head kernel (it zeroes the granule words); the
     // idle-window prefetch workgroups ride on k_row_norm, so the knob (key 7) keeps the one-workgroup form
     [[maybe_unused]] const bool norm4 = g_la_norm4 && !batch && !g_la_split_head_tail && pf_kib == 0 && (c.hidden & 15) == 0;
@@ -456,10 +483,11 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
             // layers > 0: the input norm (residual + down-projection slabs of the previous layer) runs inside this launch
             FusedNorm fq{m->slabs, m->down_ks, m->h, L.norm1, c.hidden, c.rms_eps, cf, m->fuse_cnt + 2 * l, (m->fuse & 16) ? 1 : 0};
             KCHK(lk_gemm64r_qkv(st, L.wqkv, m->xp, c.n_heads, c.n_kv_heads, c.hidden, c.balanced_wg[0], m->pos,
-                                m->w.rope_cos, m->w.rope_sin, m->qf, kf, vf, ((m->fuse & 2) && l > 0) ? &fq : nullptr, L.qkv_bias));
+                                m->w.rope_cos, m->w.rope_sin, m->qf, kf, vf, ((m->fuse & 2) && l > 0) ? &fq : nullptr, L.qkv_bias,
+                                w8 ? L.wqkv_scale : nullptr));
         } else if (m->qkv_fused) {
             KCHK(lk_gemm64_qkv(st, L.wqkv, m->xp, c.n_heads, c.n_kv_heads, c.hidden, m->pos, m->w.rope_cos, m->w.rope_sin,
-                               m->qf, kf, vf, m->qkv_rb >> 8, L.qkv_bias));
+                               m->qf, kf, vf, m->qkv_rb >> 8, L.qkv_bias, w8 ? L.wqkv_scale : nullptr));
         } else {
             KCHK(lk_gemm64_slab(st, L.wqkv, m->xp, m->qkv_n, c.hidden, m->qkv_rb, m->qkv_ks, m->slabs));
             P(KC_OTHER);
@@ -480,7 +508,7 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
                                 kf, vf, m->rowmask, m->bstate, c.n_heads, c.n_kv_heads, c.max_keys, m->n_slots, bsplit > 0 ? bsplit : m->nsplit,
                                 m->opart, m->mpart, m->lpart, m->attn_xp, c.sliding_window, ring, &pd, c.head_dim));
 #if LA_LAB
-        else if (g_la_attn_merge_ns > 0 && !long_ctx && c.n_experts == 0 && c.sliding_window <= 0 && (m->o_k / 16) / m->o_ks == 64 &&
+        else if (g_la_attn_merge_ns > 0 && !w8 && !long_ctx && c.n_experts == 0 && c.sliding_window <= 0 && (m->o_k / 16) / m->o_ks == 64 &&
                  g_la_attn_merge_ns <= m->nsplit && c.hidden % 64 == 0) {
             // lab knob 33 (review item 1b): key-split attention over NS splits, NO combine launch — o_proj merges the partials on load
             KCHK(lk_tree_attn(st, m->qf, m->kmain + (size_t)l * m->kv_layer_elems, m->vmain + (size_t)l * m->kv_layer_elems,
@@ -494,17 +522,17 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
         else {
             // riders (la_lab_set key 31): the single-launch attention occupies nh * 4 CUs; the others pull o_proj's first KiB into L2
             PfDesc rd{};
-            if (g_la_attn_ride_kib > 0 && !long_ctx) lk_pf_classic(&rd, L.wo, c.hidden, m->o_k, m->o_rb, m->o_ks, g_la_attn_ride_kib, g_la_attn_ride_delay, nullptr);
+            if (g_la_attn_ride_kib > 0 && !long_ctx && !w8) lk_pf_classic(&rd, L.wo, c.hidden, m->o_k, m->o_rb, m->o_ks, g_la_attn_ride_kib, g_la_attn_ride_delay, nullptr);
             KCHK(lk_tree_attn(st, m->qf, m->kmain + (size_t)l * m->kv_layer_elems, m->vmain + (size_t)l * m->kv_layer_elems,
                               kf, vf, m->rowmask, m->state, c.n_heads, c.n_kv_heads, m->total_keys, m->nsplit,
                               m->opart, m->mpart, m->lpart, m->attn_xp, c.sliding_window, ring, &pd, long_ctx ? 0 : -1, &rd, c.head_dim));
         }
         P(KC_O);
-        if (g_la_oproj_probe && !batch)            // timing probe (lab knob 34): another o_proj geometry; numerics are NOT preserved
+        if (g_la_oproj_probe && !batch && !w8)     // timing probe (lab knob 34): another o_proj geometry; numerics are NOT preserved
             KCHK(lk_gemm64_slab(st, L.wo, m->attn_xp, c.hidden, m->o_k, (g_la_oproj_probe & 16) ? (1 | (1 << 8)) : m->o_rb,
                                 (g_la_oproj_probe & 15) ? (g_la_oproj_probe & 15) : m->o_ks, m->slabs));
         else
-        KCHK(lk_gemm64_slab(st, L.wo, m->attn_xp, c.hidden, m->o_k, m->o_rb, m->o_ks, m->slabs));
+        KCHK(lk_gemm64_slab(st, L.wo, m->attn_xp, c.hidden, m->o_k, m->o_rb, m->o_ks, m->slabs, nullptr, w8 ? L.wo_scale : nullptr));
 #if LA_LAB
     after_oproj:
 #endif
@@ -588,13 +616,14 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
             if (c.balanced_wg[1] > 0) {
                 // down_proj follows at once: its first k-tiles are pulled into L2 from the tail of the gate/up launch
                 pd = PfDesc{};
-                if (g_la_pf_tail_kib > 0 && !m->fuse) lk_pf_classic(&pd, L.wdown, c.hidden, c.ffn, m->down_rb, m->down_ks, g_la_pf_tail_kib, 0, nullptr);
+                if (g_la_pf_tail_kib > 0 && !m->fuse && !w8) lk_pf_classic(&pd, L.wdown, c.hidden, c.ffn, m->down_rb, m->down_ks, g_la_pf_tail_kib, 0, nullptr);
                 if (pd.n_consumers > c.balanced_wg[1]) pd = PfDesc{};         // one prefetching workgroup per consumer workgroup
-                KCHK(lk_gemm64r_swiglu(st, L.wgateup, m->xp, c.ffn, c.hidden, c.balanced_wg[1], m->act_xp, nullptr, nullptr, &pd));
-            } else KCHK(lk_gemm64_swiglu(st, L.wgateup, m->xp, c.ffn, c.hidden, m->act_xp, m->gu_variant));
+                KCHK(lk_gemm64r_swiglu(st, L.wgateup, m->xp, c.ffn, c.hidden, c.balanced_wg[1], m->act_xp, nullptr, nullptr, &pd,
+                                       w8 ? L.wgateup_scale : nullptr));
+            } else KCHK(lk_gemm64_swiglu(st, L.wgateup, m->xp, c.ffn, c.hidden, m->act_xp, m->gu_variant, nullptr, w8 ? L.wgateup_scale : nullptr));
         }
         P(KC_DOWN);
-        KCHK(lk_gemm64_slab(st, L.wdown, m->act_xp, c.hidden, c.ffn, m->down_rb, m->down_ks, m->slabs));
+        KCHK(lk_gemm64_slab(st, L.wdown, m->act_xp, c.hidden, c.ffn, m->down_rb, m->down_ks, m->slabs, nullptr, w8 ? L.wdown_scale : nullptr));
         P(KC_OTHER);
         if (fork && fk[3] > 0) {
             PfDesc fd{};
@@ -1200,7 +1229,8 @@ extern "C" int la_llama_profile_gateup(la_llama* m, void* stream, int iters, flo
     for (int it = 0; it <= iters; ++it) {                 // pass 0 warms up
         HIPCHK(hipEventRecord(e0, st));
         for (int l = 0; l < c.n_layers; ++l)
-            KCHK(lk_gemm64r_swiglu(st, m->layers[l].wgateup, m->xp, c.ffn, c.hidden, c.balanced_wg[1], m->act_xp));
+            KCHK(lk_gemm64r_swiglu(st, m->layers[l].wgateup, m->xp, c.ffn, c.hidden, c.balanced_wg[1], m->act_xp, nullptr, nullptr, nullptr,
+                                   c.weight_format == 1 ? m->layers[l].wgateup_scale : nullptr));
         HIPCHK(hipEventRecord(e1, st));
         HIPCHK(hipStreamSynchronize(st));
         float ms = 0;

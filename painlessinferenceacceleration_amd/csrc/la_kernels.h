@@ -37,15 +37,19 @@ void lk_pf_classic(PfDesc* d, const void* wp, int N, int K, int rbv, int ksplit,
 int lk_pf_only(hipStream_t st, const PfDesc* pf);     // the prefetch workgroups of a descriptor as their own launch (forked graph branch)
 
 int lk_pack_weight(hipStream_t st, const void* w, const void* w2, int N, int K, int interleave2, void* out);
+int lk_pack_weight8(hipStream_t st, const void* w, const void* w2, int N, int K, int interleave2, void* out);     // fp8 (WP8)
+// wscale != null (every GEMM launcher below that takes it): the image is fp8 e4m3fn (WP8 / planned-8, la_common.h) and wscale its
+// per-row fp32 scales; only the default-plan forms exist (-1 otherwise)
 int lk_pack_x(hipStream_t st, const void* x, int K, void* out);
 int lk_gemm64_slab(hipStream_t st, const void* wp, const void* xp, int N, int K, int rb, int ksplit, float* slabs,
-                   const float* route_col = nullptr);
+                   const float* route_col = nullptr, const float* wscale = nullptr);
 int lk_gemm64_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int K, void* act_xp, int variant,
-                     const float* route_col = nullptr);
+                     const float* route_col = nullptr, const float* wscale = nullptr);
 int lk_gemm64_logits(hipStream_t st, const void* wp, const void* xp, int V, int K, int rb, void* logits, float* cv, int* ci);
 int lk_logits_cand_slots(int V, int rbv);
 int lk_gemm64_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, const int* pos, const void* rcos,
-                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant, const void* qkv_bias = nullptr);
+                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant, const void* qkv_bias = nullptr,
+                  const float* wscale = nullptr);
 void lk_qkv_row_perm(int nh, int nkv, int* perm);
 int lk_gemm64r_init();
 int lk_step_head(hipStream_t st, const int* in, int* state, int* pos, uint64_t* rowmask, int* ids, const void* embed, const void* nw,
@@ -58,13 +62,15 @@ int lk_gateup_down(hipStream_t st, const void* wgu, const void* xp, int F, int K
                    int ksplit, float* slabs, int* counter, int dd, const FusedNorm* fn = nullptr);
 int lk_rowplan(int kind, int n_rows, int n_wg, int* out);
 long lk_planned_elems(int kind, int n_rows, int K, int n_wg);
-int lk_pack_planned(hipStream_t st, const void* w, const void* w2, const int* d_plan, int kind, int n_rows, int K, int n_wg, void* out);
+int lk_pack_planned(hipStream_t st, const void* w, const void* w2, const int* d_plan, int kind, int n_rows, int K, int n_wg, void* out,
+                    int w8 = 0);      // w8 = 1: fp8 source and image (planned-8), the same chunk indices in 8-byte units
 int lk_gemm64r_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int K, int n_wg, void* act_xp,
-                      const float* route_col = nullptr, const FusedNorm* fn = nullptr, const PfDesc* pf = nullptr);
+                      const float* route_col = nullptr, const FusedNorm* fn = nullptr, const PfDesc* pf = nullptr,
+                      const float* wscale = nullptr);
 int lk_gemm64r_logits(hipStream_t st, const void* wp, const void* xp, int V, int K, int n_wg, void* logits, float* cv, int* ci);
 int lk_gemm64r_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, int n_wg, const int* pos,
                    const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn = nullptr,
-                   const void* qkv_bias = nullptr);
+                   const void* qkv_bias = nullptr, const float* wscale = nullptr);
 int lk_argmax_finalize(hipStream_t st, const float* cv, const int* ci, int n_tiles, int* out_rows);
 int lk_embed_norm(hipStream_t st, const void* embed, const int* ids, const void* nw, int hidden, float eps, void* h, void* xp,
                   int cast_first = 0, const PfDesc* pf = nullptr);

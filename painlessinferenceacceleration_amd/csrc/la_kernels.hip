@@ -54,6 +54,45 @@ __global__ void k_pack_planned(const bf16_t* __restrict__ w, const bf16_t* __res
     *(bf16x8*)(out + gid * 8) = v;
 }
 
+// fp8 forms of the two packers (WP8 / planned-8, la_common.h): the same element order with 1-byte elements, one thread per 8 bytes
+__global__ void k_pack_weight8(const uint8_t* __restrict__ w, const uint8_t* __restrict__ w2, int N, int K,
+                               int interleave2, uint8_t* __restrict__ out) {
+    const int K16 = K >> 4;
+    const int NB = interleave2 ? (2 * N) >> 5 : N >> 5;
+    size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    size_t total = (size_t)NB * K16 * 64;
+    if (gid >= total) return;
+    int lane = (int)(gid & 63);
+    size_t tile = gid >> 6;
+    int kb = (int)(tile % K16);
+    int nb = (int)(tile / K16);
+    const uint8_t* src = w;
+    int row_blk = nb;
+    if (interleave2) { src = (nb & 1) ? w2 : w; row_blk = nb >> 1; }
+    int n = row_blk * 32 + (lane & 31);
+    int k = kb * 16 + (lane >> 5) * 8;
+    *(u32x2*)(out + gid * 8) = *(const u32x2*)(src + (size_t)n * K + k);
+}
+__global__ void k_pack_planned8(const uint8_t* __restrict__ w, const uint8_t* __restrict__ w2, const int* __restrict__ plan,
+                                PackPlanArgs pa, uint8_t* __restrict__ out) {
+    size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (size_t)pa.n_wg * pa.wg_chunks) return;
+    const int wgi = (int)(gid / pa.wg_chunks);
+    int c = (int)(gid % pa.wg_chunks);
+    int rb = 0;
+    while (rb + 1 < pa.RB && c >= pa.boff[rb + 1]) ++rb;
+    c -= pa.boff[rb];
+    const int nv = pa.nv[rb];
+    const int kb = c / (2 * nv), rem = c % (2 * nv), h = rem / nv, r = rem % nv;
+    int src = plan[(wgi * pa.RB + rb) * 32 + r];
+    const uint8_t* base = w;
+    if (src >= pa.n_rows) { base = w2; src -= pa.n_rows; }
+    const int K = pa.K16 * 16;
+    u32x2 v = {0u, 0u};
+    if (src >= 0) v = *(const u32x2*)(base + (size_t)src * K + kb * 16 + h * 8);      // -1 = alignment pad row
+    *(u32x2*)(out + gid * 8) = v;
+}
+
 __global__ void k_pack_x(const bf16_t* __restrict__ x, int K, bf16_t* __restrict__ out) {
     int gid = blockIdx.x * blockDim.x + threadIdx.x;   // one thread per (t, k8)
     int K8 = K >> 3;
@@ -406,10 +445,13 @@ __device__ __forceinline__ void wave_krange(int t0, int twg, int wave, int kskew
 // HW = true: the x operand is produced by OTHER workgroups of the same launch (role-fused launches, k_gateup_down): the first
 // weight tile-sets are requested, then the wave waits for ho_counter == ho_target (handover_wait), then loads x.
 struct BlockPos { int bx, by, bz, gx, gy; };
-template <int RB, int EPI, int D, int NW, bool HW = false>
+// W8 = true: the image holds fp8 (e4m3fn) weights in the same fragment order with 1-byte elements (WP8, la_common.h) and wsc its
+// per-row fp32 scales; the loop streams the same k-tiles in the same MFMA order, converting each fragment in registers.
+template <int RB, int EPI, int D, int NW, bool HW = false, bool W8 = false>
 __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, const bf16_t* xp_s,
                                             const float* __restrict__ route_col_s, int K16_s, int kfl, const GemmArgs& a,
-                                            const BlockPos bp, float* red_, int* ho_counter, int ho_target) {
+                                            const BlockPos bp, float* red_, int* ho_counter, int ho_target,
+                                            const float* __restrict__ wsc = nullptr) {
     float (*red)[RB * 2 * 16 * 64] = (float (*)[RB * 2 * 16 * 64])red_;
     const int ex = (kfl & 1) ? bp.bz : 0;
     if (expert_unused(route_col_s ? route_col_s + ex : nullptr)) return;
@@ -431,7 +473,8 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
 
     // integer offsets from the kernel-argument bases (not mutated pointers) keep the loads in the global
     // address space: a loop-carried pointer degrades to flat_load, which ties vmcnt and lgkmcnt together
-    const bf16x8* __restrict__ wbase = (const bf16x8*)(wp_s + ((kfl & 1) ? (size_t)ex * a.ex_w : (size_t)0));
+    typedef typename std::conditional<W8, u32x2, bf16x8>::type wfrag_t;   // one lane's fragment of a k-tile: 8 or 16 bytes
+    const wfrag_t* __restrict__ wbase = (const wfrag_t*)(wp_s + ((kfl & 1) ? (size_t)ex * a.ex_w : (size_t)0));
     typedef const bf16x8* __restrict__ xptr_r;
     typedef const bf16x8* xptr_n;                                       // HW: written by other workgroups of this launch
     typename std::conditional<HW, xptr_n, xptr_r>::type xbase = (const bf16x8*)(xp_s + ((kfl & 1) ? (size_t)ex * a.ex_x : (size_t)0));
@@ -454,7 +497,8 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
         // s_waitcnt vmcnt((D-1)*(RB+2)).  Throughput of a weight-streaming wave = bytes in flight / latency,
         // so D is chosen to fill the 256-VGPR budget.  Slots past the end of the range reload the wave's
         // first tile (always valid memory) and their MFMAs are skipped by a wave-uniform branch.
-        bf16x8 fa[D][RB], fb[D][2];
+        wfrag_t fa[D][RB];
+        bf16x8 fb[D][2];
         const int n1 = ngroups == 1 ? last_valid : D;     // valid slots of group 0
         if constexpr (HW) {
 #pragma unroll
@@ -487,8 +531,9 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
             for (int d = 0; d < D; ++d) {
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
-                    acc[rb][0] = LA_MFMA(fa[d][rb], fb[d][0], acc[rb][0], 0, 0, 0);
-                    acc[rb][1] = LA_MFMA(fa[d][rb], fb[d][1], acc[rb][1], 0, 0, 0);
+                    const bf16x8 wa = wfrag<W8>(fa[d][rb]);
+                    acc[rb][0] = LA_MFMA(wa, fb[d][0], acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = LA_MFMA(wa, fb[d][1], acc[rb][1], 0, 0, 0);
                 }
                 const int dd = (d < nv ? g * D + d : 0);
 #pragma unroll
@@ -503,8 +548,9 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
             if (d < last_valid) {
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
-                    acc[rb][0] = LA_MFMA(fa[d][rb], fb[d][0], acc[rb][0], 0, 0, 0);
-                    acc[rb][1] = LA_MFMA(fa[d][rb], fb[d][1], acc[rb][1], 0, 0, 0);
+                    const bf16x8 wa = wfrag<W8>(fa[d][rb]);
+                    acc[rb][0] = LA_MFMA(wa, fb[d][0], acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = LA_MFMA(wa, fb[d][1], acc[rb][1], 0, 0, 0);
                 }
             }
         }
@@ -555,6 +601,21 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
 #pragma unroll
             for (int j = 0; j < 4; ++j) fin[rb][gg][j] = v[j];
         }
+    if constexpr (W8) {
+        // the per-row scales, once, in fp32, before anything else of the epilogue (rows of this lane: 4 consecutive features)
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+            for (int gg = 0; gg < GPW; ++gg) {
+                int si;
+                if constexpr (EPI == EPI_SWIGLU) si = rb * a.N + bp.bx * 32 + 8 * (g0 + gg) + 4 * hh;          // gate rows, then up rows
+                else if constexpr (EPI == EPI_QKV) si = (bp.bx >> 1) * 128 + 64 * rb + 32 * (bp.bx & 1) + 8 * (g0 + gg) + 4 * hh;
+                else si = (nb0 + rb) * 32 + 8 * (g0 + gg) + 4 * hh;
+                const f32x4 s4 = *(const f32x4*)(wsc + si);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) fin[rb][gg][j] *= s4[j];
+            }
+    }
     const int tok = tb * 32 + tl;
     if constexpr (EPI == EPI_SLAB) {
         float* o = a.slabs + (size_t)ex * a.ex_slab + (size_t)ks * LA_TB * a.N;
@@ -663,6 +724,15 @@ __global__ __launch_bounds__(NW * 64) void k_gemm64(const bf16_t* __restrict__ w
     const BlockPos bp = {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y};
     gemm64_body<RB, EPI, D, NW, false>(wp_s, xp_s, route_col_s, K16_s, kfl, a, bp, &red[0][0], nullptr, 0);
 }
+// fp8 weights (WP8 image + per-row scales wsc): its own kernel, so that the 16-bit kernels keep their argument block and code
+template <int RB, int EPI, int D, int NW>
+__global__ __launch_bounds__(NW * 64) void k_gemm64_w8(const bf16_t* __restrict__ wp_s, const bf16_t* __restrict__ xp_s,
+                                                        const float* __restrict__ route_col_s, int K16_s, int kfl, GemmArgs a,
+                                                        const float* __restrict__ wsc) {
+    __shared__ __attribute__((aligned(16))) float red[NW][RB * 2 * 16 * 64];
+    const BlockPos bp = {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y};
+    gemm64_body<RB, EPI, D, NW, false, true>(wp_s, xp_s, route_col_s, K16_s, kfl, a, bp, &red[0][0], nullptr, 0, wsc);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Balanced skinny GEMM ("one workgroup per CU"): the per-CU streaming rate is capped (~22 GB/s of the chip's
@@ -694,11 +764,12 @@ struct GemmRArgs {
 };
 
 // Leading scalars = the prologue's operands (kernarg preload, see k_gemm64): nvl_pk = nvl[0..3] one byte each.
-template <int RB, int EPI, int D, int NW, int NSF = 0>
+// W8 = true: planned-8 image (la_common.h) + per-row fp32 scales wsc, as gemm64_body
+template <int RB, int EPI, int D, int NW, int NSF = 0, bool W8 = false>
 __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, const bf16_t* xp_s,
                                              const float* __restrict__ route_col_s, int K16_s, int kfl, int wg_chunks_s,
                                              unsigned nvl_pk, int boff0, int boff1, int boff2, int boff3, const GemmRArgs& ra,
-                                             const BlockPos bp, float* redr) {
+                                             const BlockPos bp, float* redr, const float* __restrict__ wsc = nullptr) {
     const GemmArgs& a = ra.g;
     const int ex = (kfl & 1) ? bp.by : 0;
     if (expert_unused(route_col_s ? route_col_s + ex : nullptr)) return;
@@ -712,7 +783,8 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
     if (NW == 8 && prio_hi > 0 && wave >= 4) { if (prio_hi == 1) __builtin_amdgcn_s_setprio(1); else if (prio_hi == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
     const int ngroups = (cnt + D - 1) / D;
     const int last_valid = cnt - (ngroups - 1) * D;
-    const bf16x8* __restrict__ wbase = (const bf16x8*)(wp_s + ((kfl & 1) ? (size_t)ex * a.ex_w : (size_t)0));
+    typedef typename std::conditional<W8, u32x2, bf16x8>::type wfrag_t;   // one lane's fragment of a k-tile: 8 or 16 bytes
+    const wfrag_t* __restrict__ wbase = (const wfrag_t*)(wp_s + ((kfl & 1) ? (size_t)ex * a.ex_w : (size_t)0));
     typedef const bf16x8* __restrict__ xptr_r;
     typedef const bf16x8* xptr_n;                                       // fused producers write g.xp inside this kernel
     typename std::conditional<(NSF > 0), xptr_n, xptr_r>::type xbase = (const bf16x8*)xp_s;
@@ -735,7 +807,8 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[rb][tb][i] = 0.f;
     if (ngroups > 0) {
-        bf16x8 fa[D][RB], fb[D][2];
+        wfrag_t fa[D][RB];
+        bf16x8 fb[D][2];
         const int n1 = ngroups == 1 ? last_valid : D;
         if constexpr (NSF > 0) {
             // The activations do not exist yet.  Producers run the row stage BEFORE touching their weights (a wave's loads
@@ -785,8 +858,9 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
             for (int d = 0; d < D; ++d) {
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
-                    acc[rb][0] = LA_MFMA(fa[d][rb], fb[d][0], acc[rb][0], 0, 0, 0);
-                    acc[rb][1] = LA_MFMA(fa[d][rb], fb[d][1], acc[rb][1], 0, 0, 0);
+                    const bf16x8 wa = wfrag<W8>(fa[d][rb]);
+                    acc[rb][0] = LA_MFMA(wa, fb[d][0], acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = LA_MFMA(wa, fb[d][1], acc[rb][1], 0, 0, 0);
                 }
                 const int dd = (d < nv2 ? g * D + d : 0);
 #pragma unroll
@@ -801,8 +875,9 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
             if (d < last_valid) {
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
-                    acc[rb][0] = LA_MFMA(fa[d][rb], fb[d][0], acc[rb][0], 0, 0, 0);
-                    acc[rb][1] = LA_MFMA(fa[d][rb], fb[d][1], acc[rb][1], 0, 0, 0);
+                    const bf16x8 wa = wfrag<W8>(fa[d][rb]);
+                    acc[rb][0] = LA_MFMA(wa, fb[d][0], acc[rb][0], 0, 0, 0);
+                    acc[rb][1] = LA_MFMA(wa, fb[d][1], acc[rb][1], 0, 0, 0);
                 }
             }
         }
@@ -864,6 +939,10 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                 xl += red4[(((tbe * NW + p) * RB + 0) * 4 + gi) * 64 + lane];
                 xh += red4[(((tbe * NW + p) * RB + 1) * 4 + gi) * 64 + lane];
             }
+            if constexpr (W8) {          // per-row scales (lane-ordered: 4 consecutive lanes), before the bias
+                xl *= *(const f32x4*)(wsc + slot * 128 + dlo);
+                xh *= *(const f32x4*)(wsc + slot * 128 + dhi);
+            }
             qkv_bias_add<4>(a.qkv_bias, slot * 128 + dlo, xl);
             qkv_bias_add<4>(a.qkv_bias, slot * 128 + dhi, xh);
             if (rope) {
@@ -924,10 +1003,17 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                 for (int j = 0; j < 4; ++j) {
                     const int f = 8 * gi + 4 * hh + j;
                     if (f < ra.nv[qq]) {
-                        const float gv = bfr(g4[j]), uv = bfr(u4[j]);
-                        const float sv = bfr(gv / (1.0f + expf(-gv)));
-                        const int feat = ra.R * bp.bx + 32 * qq + f;
-                        a.act_xp[(size_t)ex * a.ex_act + xp_offset(tok, feat)] = f2bf(sv * uv);
+                        if constexpr (W8) {                  // gate / up row scales first (the 16-bit branch below is the original code)
+                            const int feat = ra.R * bp.bx + 32 * qq + f;
+                            const float gv = bfr(g4[j] * wsc[feat]), uv = bfr(u4[j] * wsc[a.N + feat]);
+                            const float sv = bfr(gv / (1.0f + expf(-gv)));
+                            a.act_xp[(size_t)ex * a.ex_act + xp_offset(tok, feat)] = f2bf(sv * uv);
+                        } else {
+                            const float gv = bfr(g4[j]), uv = bfr(u4[j]);
+                            const float sv = bfr(gv / (1.0f + expf(-gv)));
+                            const int feat = ra.R * bp.bx + 32 * qq + f;
+                            a.act_xp[(size_t)ex * a.ex_act + xp_offset(tok, feat)] = f2bf(sv * uv);
+                        }
                     }
                 }
             }
@@ -943,6 +1029,7 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                     if (f < ra.nv[0]) {
                         const int pr = ra.R * bp.bx + f, slot = pr >> 6, dlo = pr & 63, dhi = dlo + 64;
                         float xl = xl4[j], xh = xh4[j];
+                        if constexpr (W8) { xl *= wsc[slot * 128 + dlo]; xh *= wsc[slot * 128 + dhi]; }
                         qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
                         qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
                         if (slot < a.nh + a.nkv) {
@@ -1020,6 +1107,16 @@ __global__ __launch_bounds__(NW * 64) void k_gemm64r(const bf16_t* __restrict__ 
     extern __shared__ __attribute__((aligned(16))) float redr[];      // [NW][RB][16][64]
     const BlockPos bp = {(int)blockIdx.x, (int)blockIdx.y, 0, (int)gridDim.x, (int)gridDim.y};
     gemm64r_body<RB, EPI, D, NW, NSF>(wp_s, xp_s, route_col_s, K16_s, kfl, wg_chunks_s, nvl_pk, boff0, boff1, boff2, boff3, ra, bp, redr);
+}
+// fp8 weights (planned-8 image + per-row scales wsc)
+template <int RB, int EPI, int D, int NW>
+__global__ __launch_bounds__(NW * 64) void k_gemm64r_w8(const bf16_t* __restrict__ wp_s, const bf16_t* xp_s,
+                                                         const float* __restrict__ route_col_s, int K16_s, int kfl, int wg_chunks_s,
+                                                         unsigned nvl_pk, int boff0, int boff1, int boff2, int boff3, GemmRArgs ra,
+                                                         const float* __restrict__ wsc) {
+    extern __shared__ __attribute__((aligned(16))) float redr[];      // [NW][RB][16][64]
+    const BlockPos bp = {(int)blockIdx.x, (int)blockIdx.y, 0, (int)gridDim.x, (int)gridDim.y};
+    gemm64r_body<RB, EPI, D, NW, 0, true>(wp_s, xp_s, route_col_s, K16_s, kfl, wg_chunks_s, nvl_pk, boff0, boff1, boff2, boff3, ra, bp, redr, wsc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1906,6 +2003,11 @@ int lk_pack_weight(hipStream_t st, const void* w, const void* w2, int N, int K, 
     k_pack_weight<<<(unsigned)((total + 255) / 256), 256, 0, st>>>((const bf16_t*)w, (const bf16_t*)w2, N, K, il, (bf16_t*)out);
     LAUNCH_CHECK(); return 0;
 }
+int lk_pack_weight8(hipStream_t st, const void* w, const void* w2, int N, int K, int il, void* out) {
+    size_t total = (size_t)(il ? 2 * N : N) / 32 * (K / 16) * 64;
+    k_pack_weight8<<<(unsigned)((total + 255) / 256), 256, 0, st>>>((const uint8_t*)w, (const uint8_t*)w2, N, K, il, (uint8_t*)out);
+    LAUNCH_CHECK(); return 0;
+}
 int lk_pack_x(hipStream_t st, const void* x, int K, void* out) {
     int total = LA_TB * (K / 8);
     k_pack_x<<<(total + 255) / 256, 256, 0, st>>>((const bf16_t*)x, K, (bf16_t*)out);
@@ -1929,18 +2031,34 @@ static int launch_gemm(hipStream_t st, const GemmArgs& a, int nblocks, int kspli
     LAUNCH_CHECK(); return 0;
 }
 
+// fp8 launches (wscale != null: a WP8 / planned-8 image and its per-row scales).  Only the forms the default plan of the step uses
+// exist; anything else is -1 rather than a 16-bit kernel reading 1-byte weights.  D (tile-sets in flight) is re-picked for the
+// bytes in flight: an fp8 tile-set carries half the weight bytes and the same x fragments.
 int lk_gemm64_slab(hipStream_t st, const void* wp, const void* xp, int N, int K, int rbv, int ksplit, float* slabs,
-                   const float* route_col) {
+                   const float* route_col, const float* wscale) {
     const int rb = rbv & 0xff, variant = rbv >> 8;
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = N; a.slabs = slabs;
     a.route_col = route_col; a.slab_wt = g_la_slab_wt;
+    if (wscale) {
+        if (rb != 2 || (N % 64) || route_col) return -1;
+        dim3 g(N / 64, ksplit);
+        if (variant == 3) k_gemm64_w8<2, EPI_SLAB, 12, 8><<<g, 512, 0, st>>>(G64_HEAD(a), a, wscale);       // o_proj
+        else if (variant == 0) k_gemm64_w8<2, EPI_SLAB, 16, 4><<<g, 256, 0, st>>>(G64_HEAD(a), a, wscale);  // down_proj
+        else return -1;
+        LAUNCH_CHECK(); return 0;
+    }
     if (rb == 2 && (N % 64) == 0) return launch_gemm<2, EPI_SLAB>(st, a, N / 64, ksplit, variant);
     return launch_gemm<1, EPI_SLAB>(st, a, N / 32, ksplit, variant);
 }
 int lk_gemm64_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int K, void* act_xp, int variant,
-                     const float* route_col) {
+                     const float* route_col, const float* wscale) {
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = F; a.act_xp = (bf16_t*)act_xp;
     a.route_col = route_col;
+    if (wscale) {
+        if (variant != 0 || route_col) return -1;
+        k_gemm64_w8<2, EPI_SWIGLU, 16, 4><<<dim3(F / 32, 1), 256, 0, st>>>(G64_HEAD(a), a, wscale);
+        LAUNCH_CHECK(); return 0;
+    }
     return launch_gemm<2, EPI_SWIGLU>(st, a, F / 32, 1, variant);
 }
 int lk_gemm64_logits(hipStream_t st, const void* wp, const void* xp, int V, int K, int rbv, void* logits,
@@ -1953,12 +2071,17 @@ int lk_gemm64_logits(hipStream_t st, const void* wp, const void* xp, int V, int 
 }
 // QKV projection with the RoPE / fragment epilogue.  wp must be packed from the row-permuted [Wq;Wk;Wv] (lk_qkv_row_perm).
 int lk_gemm64_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, const int* pos, const void* rcos,
-                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant, const void* qkv_bias) {
+                  const void* rsin, void* qf, void* kfresh, void* vfresh, int variant, const void* qkv_bias, const float* wscale) {
     if (qkv_bias && g_la_dbg_noepi) return -1;          // the timing probe writes no epilogue: it would drop the bias
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = (nh + 2 * nkv) * 128;
     a.pos = pos; a.rcos = (const bf16_t*)rcos; a.rsin = (const bf16_t*)rsin;
     a.qf = (bf16_t*)qf; a.kfresh = (bf16_t*)kfresh; a.vfresh = (bf16_t*)vfresh; a.nh = nh; a.nkv = nkv;
     a.qkv_bias = (const bf16_t*)qkv_bias;
+    if (wscale) {
+        if (variant != 0) return -1;
+        k_gemm64_w8<2, EPI_QKV, 16, 4><<<dim3(a.N / 64, 1), 256, 0, st>>>(G64_HEAD(a), a, wscale);
+        LAUNCH_CHECK(); return 0;
+    }
     return launch_gemm<2, EPI_QKV>(st, a, a.N / 64, 1, variant);
 }
 // packed row r of the permuted QKV matrix <- original row perm[r]: workgroup b = r/64 holds head slot b>>1, dims
@@ -2035,7 +2158,8 @@ void lk_pf_classic(PfDesc* d, const void* wp, int N, int K, int rbv, int ksplit,
     d->RB = RB; d->NW = NW; d->delay = delay; d->magic = 0x5bd1e995u; d->sink = sink;
 }
 // planned packing (see k_pack_planned): kind as lk_rowplan
-int lk_pack_planned(hipStream_t st, const void* w, const void* w2, const int* d_plan, int kind, int n_rows, int K, int n_wg, void* out) {
+int lk_pack_planned(hipStream_t st, const void* w, const void* w2, const int* d_plan, int kind, int n_rows, int K, int n_wg, void* out,
+                    int w8) {
     GemmRArgs ra{}; ra.g.K16 = K / 16;
     PackPlanArgs pa{}; pa.n_wg = n_wg; pa.K16 = K / 16; pa.n_rows = n_rows;
     if (kind == 2) { const int pairs = n_rows / 2; ra.R = pairs / n_wg; ra.nv[0] = ra.nv[1] = ra.R; pa.RB = 2;
@@ -2046,7 +2170,8 @@ int lk_pack_planned(hipStream_t st, const void* w, const void* w2, const int* d_
     for (int i = 0; i < 4; ++i) { pa.nv[i] = ra.nvl[i]; pa.boff[i] = ra.boff[i]; }
     pa.wg_chunks = ra.wg_chunks;
     size_t total = (size_t)n_wg * pa.wg_chunks;
-    k_pack_planned<<<(unsigned)((total + 255) / 256), 256, 0, st>>>((const bf16_t*)w, (const bf16_t*)w2, d_plan, pa, (bf16_t*)out);
+    if (w8) k_pack_planned8<<<(unsigned)((total + 255) / 256), 256, 0, st>>>((const uint8_t*)w, (const uint8_t*)w2, d_plan, pa, (uint8_t*)out);
+    else k_pack_planned<<<(unsigned)((total + 255) / 256), 256, 0, st>>>((const bf16_t*)w, (const bf16_t*)w2, d_plan, pa, (bf16_t*)out);
     LAUNCH_CHECK(); return 0;
 }
 static bool set_fused_norm(GemmRArgs& ra, const FusedNorm* fn, int n_wg) {
@@ -2057,11 +2182,16 @@ static bool set_fused_norm(GemmRArgs& ra, const FusedNorm* fn, int n_wg) {
     return true;
 }
 int lk_gemm64r_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int K, int n_wg, void* act_xp,
-                      const float* route_col, const FusedNorm* fn, const PfDesc* pf) {
+                      const float* route_col, const FusedNorm* fn, const PfDesc* pf, const float* wscale) {
     GemmRArgs ra{}; ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times; ra.g.wp = (const bf16_t*)wp; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = F; ra.g.act_xp = (bf16_t*)act_xp;
     ra.g.route_col = route_col;
     ra.R = F / n_wg; if (F % n_wg || ra.R > 64 || ra.R <= 32) return -1;
     fill_nv(ra, ra.R, 2, 2);
+    if (wscale) {          // fp8: no fused norm, no expert routing, no tail prefetch (its descriptors count 16-bit bytes)
+        if ((fn && fn->counter) || route_col || pf_extra(pf) || lk_gemm64r_init() != 0) return -1;
+        k_gemm64r_w8<4, EPI_SWIGLU, 6, 8><<<n_wg, 512, 8 * 4 * 4096, st>>>(G64R_HEAD(ra), ra, wscale);
+        LAUNCH_CHECK(); return 0;
+    }
     if (pf_extra(pf)) ra.pf = *pf;
     if (set_fused_norm(ra, fn, n_wg)) {
         if (fn->n_slabs != 4 || route_col) return -1;
@@ -2085,7 +2215,8 @@ int lk_gemm64r_logits(hipStream_t st, const void* wp, const void* xp, int V, int
     LAUNCH_CHECK(); return 0;
 }
 int lk_gemm64r_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nkv, int K, int n_wg, const int* pos,
-                   const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn, const void* qkv_bias) {
+                   const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn, const void* qkv_bias,
+                   const float* wscale) {
     if (qkv_bias && g_la_dbg_noepi) return -1;          // the timing probe writes no epilogue: it would drop the bias
     GemmRArgs ra{}; ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times; ra.g.wp = (const bf16_t*)wp; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = (nh + 2 * nkv) * 128;
     ra.g.pos = pos; ra.g.rcos = (const bf16_t*)rcos; ra.g.rsin = (const bf16_t*)rsin;
@@ -2096,6 +2227,11 @@ int lk_gemm64r_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int n
     ra.nv[0] = ra.nv[1] = ra.R;
     ra.nvl[0] = ra.nvl[1] = (ra.R + 3) & ~3;
     ra.boff[0] = 0; ra.boff[1] = ra.nvl[0] * 2 * ra.g.K16; ra.wg_chunks = 2 * ra.boff[1];
+    if (wscale) {
+        if ((fn && fn->counter) || lk_gemm64r_init() != 0) return -1;
+        k_gemm64r_w8<2, EPI_QKV, 12, 8><<<n_wg, 512, 2 * 8 * 2 * 4096, st>>>(G64R_HEAD(ra), ra, wscale);
+        LAUNCH_CHECK(); return 0;
+    }
     if (set_fused_norm(ra, fn, n_wg)) {
         if (fn->n_slabs != 4) return -1;
         k_gemm64r<2, EPI_QKV, 8, 8, 4><<<n_wg, 512, 2 * 8 * 2 * 4096, st>>>(G64R_HEAD(ra), ra);
@@ -2141,6 +2277,8 @@ int lk_gemm64r_init() {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<2, EPI_QKV, 8, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 2 * 4096);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4 * 4096);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r_w8<4, EPI_SWIGLU, 6, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r_w8<2, EPI_QKV, 12, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 2 * 4096);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gateup_down<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gateup_down<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gateup_down<2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);

@@ -238,6 +238,106 @@ def check_biases(shape, state_dict):
             raise ValueError(f'the state dict carries {k}: {why}; refusing to drop it')
 
 
+FP8_MAX = 448.0          # largest finite e4m3fn value
+PROJECTIONS = ('self_attn.q_proj', 'self_attn.k_proj', 'self_attn.v_proj', 'self_attn.o_proj', 'mlp.gate_proj', 'mlp.up_proj',
+               'mlp.down_proj')
+_W16_NAMES = ('storage', 'bf16', 'bfloat16', 'fp16', 'float16')
+
+
+def quantize_fp8(w):
+    """Per-output-row symmetric FP8 (OCP e4m3fn) quantization: s[n] = amax(|W[n, :]|) / 448, q = clamp(W / s, -448, 448) in e4m3fn,
+    so that W'[n][k] = s[n] * q[n][k].  A row whose amax is 0 (lane padding) gets s = 1 and q = 0.  The clamp matters: torch's cast
+    gives NaN above ~464 rather than saturating, and W / s can round just past 448.  -> (q float8_e4m3fn [N, K], s float32 [N])."""
+    w = w.float()
+    amax = w.abs().amax(dim=1)
+    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    q = (w / s[:, None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q, s
+
+
+def dequantize_fp8(q, s):
+    """W' = s[n] * q[n][k] in fp32 (what an fp8 engine computes with)."""
+    return q.float() * s.float().reshape(-1, 1)
+
+
+def fp8_row_scale(scale, n_rows, name):
+    """A checkpoint's weight_scale -> fp32 [n_rows]: a scalar per tensor is broadcast to the rows, [N] / [N, 1] is per channel."""
+    scale = scale.detach().float().reshape(-1)
+    if scale.numel() == 1:
+        return scale.expand(n_rows).clone()
+    if scale.numel() != n_rows:
+        raise ValueError(f'{name}: {scale.numel()} scales for {n_rows} rows (per-tensor or per-output-row scales only)')
+    return scale.clone()
+
+
+def fp8_lanes(q, s, n_h, dim, lane_src):
+    """The 128-feature lanes (la_head_lane_map) of an fp8 projection of a model with head_dim < 128: q (uint8 view of the e4m3fn
+    bytes: torch has no fp8 multiply) rows (dim 0: q / k / v) or columns (dim 1: o_proj) spread over the lanes, zero on padding
+    lanes; s (fp32 per output row) follows the rows, padding rows get s = 1.  -> (q, s)."""
+    hd = int((lane_src >= 0).sum())
+    if hd == 128:
+        return q, s
+    src = torch.from_numpy(lane_src.astype(np.int64)).to(q.device)
+    idx = (torch.arange(n_h, device=q.device)[:, None] * hd + src.clamp(min=0)[None, :]).reshape(-1)
+    keep = (src >= 0).repeat(n_h)
+    shape_ = [1, 1]
+    shape_[dim] = -1
+    q = q.index_select(dim, idx) * keep.reshape(shape_).to(q.dtype)
+    if dim == 0:
+        s = torch.where(keep.to(s.device), s.index_select(0, idx.to(s.device)), torch.ones((), dtype=s.dtype, device=s.device))
+    return q, s
+
+
+def check_weight_format(shape, state_dict, weight_format=None, gemm_cfg=None, fuse=0, max_blocks=0):
+    """-> 'fp8' or None (the storage type).  weight_format=None: the state dict decides — float8_e4m3fn projections with their
+    <proj>.weight_scale select fp8 by themselves; 'fp8' quantizes 16/32-bit projections at load (quantize_fp8).  Everything the fp8
+    launches cannot serve is REFUSED here, before any GPU is needed (la_llama_create refuses the same cases as a second line)."""
+    if weight_format is not None and weight_format != 'fp8' and weight_format not in _W16_NAMES:
+        raise ValueError(f"weight_format={weight_format!r}: None, 'fp8' or a 16-bit name {_W16_NAMES}")
+    sd = state_dict or {}
+    blockwise = [k for k in sd if k.endswith('.weight_scale_inv')]
+    if blockwise:
+        raise ValueError(f'{blockwise[0]}: block-wise fp8 scales (128x128 blocks) are not supported; per-tensor or per-row weight_scale only')
+    kinds = {}
+    for k, v in sd.items():
+        if any(k.endswith(f'.{p}.weight') for p in PROJECTIONS) and k.startswith('model.layers.'):
+            kinds.setdefault(v.dtype == torch.float8_e4m3fn, k)
+            if v.dtype == torch.float8_e4m3fn and k[:-len('weight')] + 'weight_scale' not in sd:
+                raise ValueError(f'{k} is float8_e4m3fn but the state dict has no {k[:-len("weight")]}weight_scale')
+        elif k.endswith('.weight_scale') and k[:-len('_scale')] in sd and sd[k[:-len('_scale')]].dtype != torch.float8_e4m3fn:
+            raise ValueError(f'{k} belongs to a {sd[k[:-len("_scale")]].dtype} weight: scales come with float8_e4m3fn weights only')
+    # every other 8-bit float tensor (lm_head, embedding, norms, MoE experts, another fp8 encoding) has no fp8 consumer: the 16-bit
+    # path would cast it to the storage type without its scale, i.e. compute another model
+    f8 = tuple(getattr(torch, n) for n in ('float8_e4m3fn', 'float8_e5m2', 'float8_e4m3fnuz', 'float8_e5m2fnuz') if hasattr(torch, n))
+    for k, v in sd.items():
+        if torch.is_tensor(v) and v.dtype in f8 and not (v.dtype == torch.float8_e4m3fn and k.startswith('model.layers.')
+                                                         and any(k.endswith(f'.{p}.weight') for p in PROJECTIONS)):
+            raise ValueError(f'{k} is {v.dtype}: fp8 weights are supported for the q/k/v, o, gate/up and down projections only '
+                             '(OCP e4m3fn with weight_scale); refusing to cast it without its scale')
+    if len(kinds) > 1:
+        raise ValueError(f'mixed weight formats: {kinds[True]} is float8_e4m3fn, {kinds[False]} is not; the projections must share one format')
+    pre = kinds.get(True) is not None
+    if pre and weight_format in _W16_NAMES:
+        raise ValueError(f'weight_format={weight_format!r} but the projections are float8_e4m3fn ({kinds[True]}); they are not dequantized silently')
+    fmt = 'fp8' if (pre or weight_format == 'fp8') else None
+    if fmt is None:
+        return None
+    if getattr(shape, 'n_experts', 0) > 0:
+        raise ValueError('fp8 weights: MoE (Mixtral) experts have no fp8 launch')
+    if max_blocks > 1:
+        raise ValueError('fp8 weights: the multi-block step (max_blocks > 1) has no fp8 launch')
+    if fuse:
+        raise ValueError('fp8 weights: the fused norm / role-fused launches (fuse != 0) have no fp8 form')
+    g = list(gemm_cfg or []) + [0] * 8
+    if g[1] < 0:
+        raise ValueError('fp8 weights: the unfused QKV (gemm_cfg[1] < 0) has no fp8 launch')
+    if (g[0] >> 8) != 0 or g[2] not in (0, 2, 2 | 3 << 8) or g[4] not in (0, 2, 2 | 3 << 8) or g[7] != 0:
+        raise ValueError(f'fp8 weights: only the default GEMM plan has fp8 launches (gemm_cfg={list(gemm_cfg)})')
+    if shape.hidden % 64:
+        raise ValueError('fp8 weights: hidden must be a multiple of 64')
+    return fmt
+
+
 DEFAULT_LAB = False      # engines created without lab=... take the product library; the lab_build fixture of tests/conftest.py flips it for a variant test
 
 
@@ -247,8 +347,12 @@ class LlamaVerifyEngine(object):
     verify block are shared by the active slots (bstep)."""
 
     def __init__(self, shape, state_dict, max_length=2048, device='cuda:0', attn_split=0, gemm_cfg=None,
-                 consume_state_dict=False, balanced=True, n_slots=1, fuse=0, max_blocks=0, kv_ring=False, dtype=None, lab=None):
+                 consume_state_dict=False, balanced=True, n_slots=1, fuse=0, max_blocks=0, kv_ring=False, dtype=None, lab=None,
+                 weight_format=None):
         check_biases(shape, state_dict)
+        # weight_format: None (the state dict decides) or 'fp8' — W8A16, see check_weight_format / quantize_fp8
+        self.weight_format = check_weight_format(shape, state_dict, weight_format, gemm_cfg, fuse, max_blocks)
+        w8 = self.weight_format == 'fp8'
         if not torch.cuda.is_available():
             raise RuntimeError('LlamaVerifyEngine needs an MI355X: the verify step has no CPU fallback')
         # The engine computes in the checkpoint's own 16-bit type: bfloat16 (BASELINE) or float16 (what the reference's examples and
@@ -305,6 +409,7 @@ class LlamaVerifyEngine(object):
             shape_[dim] = -1
             return out * keep.reshape(shape_).to(out.dtype)
         self._keep = []
+        self._img_bytes = 0          # bytes of the packed weight images (+ fp8 scales) built so far: weight_bytes below
 
         def dev(t):
             t = t.to(device=self.device, dtype=self.dtype).contiguous()
@@ -322,10 +427,43 @@ class LlamaVerifyEngine(object):
                                      1 if w2 is not None else 0, out.data_ptr()), 'pack_weight')
             self.stream.synchronize()                    # w / w2 may be freed by the caller right after
             self._keep.append(out)
+            self._img_bytes += out.numel() * out.element_size()
             return out
 
         def take(name):
             return state_dict.pop(name) if consume_state_dict else state_dict[name]
+
+        def take_fp8(name):
+            """projection `name` (…/q_proj etc.) -> (q as uint8 [N, K] on the device, s fp32 [N]): the checkpoint's own e4m3fn bytes and
+            weight_scale, or quantize_fp8 of a 16/32-bit weight"""
+            w = take(name + '.weight')
+            if w.dtype == torch.float8_e4m3fn:
+                q, sc = w.to(self.device), fp8_row_scale(take(name + '.weight_scale'), w.shape[0], name).to(self.device)
+            else:
+                q, sc = quantize_fp8(w.to(self.device))
+            if consume_state_dict:
+                state_dict.pop(name + '.input_scale', None)        # activations stay 16-bit (W8A16)
+            return q.view(torch.uint8).contiguous(), sc.float().contiguous()
+
+        def keep32(t):
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+            self._keep.append(t)
+            self._img_bytes += t.numel() * t.element_size()
+            return t
+
+        def pack8(w, w2=None):
+            n, k = w.shape
+            out = torch.empty((2 if w2 is not None else 1) * n * k, dtype=torch.uint8, device=self.device)
+            torch.cuda.synchronize(self.device)
+            check(self._lib.la_pack_weight_fp8(sp, w.data_ptr(), w2.data_ptr() if w2 is not None else None, n, k,
+                                               1 if w2 is not None else 0, out.data_ptr()), 'pack_weight_fp8')
+            self.stream.synchronize()
+            self._keep.append(out)
+            self._img_bytes += out.numel() * out.element_size()
+            return out
+
+        def lanes8(q, sc, n_h, dim):
+            return fp8_lanes(q, sc, n_h, dim, lane_src)
 
         # Balanced GEMMs: one workgroup per CU, rows dealt out by la_rowplan (0 = shape not balanceable -> classic grid)
         n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
@@ -366,6 +504,19 @@ class LlamaVerifyEngine(object):
                     plan_kinds['qkv_mb'] = (2, 2 * pairs, want)
                     self.qkv_mb_wg = want
 
+        def pack_planned8(slot, mats):
+            """la_pack_planned_fp8: the planned image with 1-byte elements"""
+            kind, n_rows, nwg = plan_kinds[slot]
+            K = mats[0].shape[1]
+            out = torch.empty(self._lib.la_planned_elems(kind, n_rows, K, nwg), dtype=torch.uint8, device=self.device)
+            torch.cuda.synchronize(self.device)
+            check(self._lib.la_pack_planned_fp8(sp, mats[0].data_ptr(), mats[1].data_ptr() if len(mats) > 1 else None,
+                                                plans[slot].data_ptr(), kind, n_rows, K, nwg, out.data_ptr()), 'pack_planned_fp8')
+            self.stream.synchronize()
+            self._keep.append(out)
+            self._img_bytes += out.numel() * out.element_size()
+            return out
+
         def pack_planned(slot, mats):
             """compact workgroup-major packing by the plan (la_pack_planned)"""
             kind, n_rows, nwg = plan_kinds[slot]
@@ -377,6 +528,7 @@ class LlamaVerifyEngine(object):
                                       plans[slot].data_ptr(), kind, n_rows, K, nwg, out.data_ptr()), 'pack_planned')
             self.stream.synchronize()
             self._keep.append(out)
+            self._img_bytes += out.numel() * out.element_size()
             return out
 
         # rows of [Wq;Wk;Wv] are gathered so that each GEMM workgroup owns RoPE pairs (d, d+64): the QKV epilogue
@@ -400,6 +552,32 @@ class LlamaVerifyEngine(object):
                 bias = torch.cat([to_lanes(b.to(self.device).reshape(-1, 1), nh_, 0).reshape(-1)
                                   for b, nh_ in ((bq, shape.n_heads), (bk, shape.n_kv_heads), (bv, shape.n_kv_heads))])
                 layers[i].qkv_bias = dev(bias).data_ptr()
+            if w8:
+                # fp8: the scales follow the rows through the lanes and the concatenation; the QKV scale vector stays lane-ordered
+                # (slot * 128 + lane) whatever row order the image gets, like the bias
+                parts = [lanes8(*take_fp8(p + f'self_attn.{n}_proj'), nh_, 0)
+                         for n, nh_ in (('q', shape.n_heads), ('k', shape.n_kv_heads), ('v', shape.n_kv_heads))]
+                q8 = torch.cat([a for a, _ in parts], 0)
+                layers[i].wqkv_scale = keep32(torch.cat([b for _, b in parts])).data_ptr()
+                if self.balanced_wg[0]:
+                    layers[i].wqkv = pack_planned8(0, [q8]).data_ptr()
+                else:
+                    layers[i].wqkv = pack8(q8.index_select(0, qkv_perm).contiguous()).data_ptr()
+                del q8, parts
+                qo, so = take_fp8(p + 'self_attn.o_proj')
+                layers[i].wo = pack8(lanes8(qo, so, shape.n_heads, 1)[0].contiguous()).data_ptr()
+                layers[i].wo_scale = keep32(so).data_ptr()
+                (qg, sg), (qu, su) = take_fp8(p + 'mlp.gate_proj'), take_fp8(p + 'mlp.up_proj')
+                layers[i].wgateup = (pack_planned8(1, [qg, qu]) if self.balanced_wg[1] else pack8(qg, qu)).data_ptr()
+                layers[i].wgateup_scale = keep32(torch.cat([sg, su])).data_ptr()
+                qd, sd_ = take_fp8(p + 'mlp.down_proj')
+                layers[i].wdown = pack8(qd).data_ptr()
+                layers[i].wdown_scale = keep32(sd_).data_ptr()
+                del qo, qg, qu, qd
+                layers[i].norm1 = dev(take(p + 'input_layernorm.weight')).data_ptr()
+                layers[i].norm2 = dev(take(p + 'post_attention_layernorm.weight')).data_ptr()
+                torch.cuda.synchronize(self.device)
+                continue
             qkv = torch.cat([to_lanes(take(p + 'self_attn.q_proj.weight').to(self.device), shape.n_heads, 0),
                              to_lanes(take(p + 'self_attn.k_proj.weight').to(self.device), shape.n_kv_heads, 0),
                              to_lanes(take(p + 'self_attn.v_proj.weight').to(self.device), shape.n_kv_heads, 0)], 0)
@@ -461,7 +639,11 @@ class LlamaVerifyEngine(object):
             self.rope_cos, self.rope_sin = padc.contiguous(), pads.contiguous()
         w = _lib.LlamaWeightsC()
         w.embed = self.embed.data_ptr()
+        proj_bytes = self._img_bytes
         w.lm_head = (pack_planned(2, [take('lm_head.weight')]) if self.balanced_wg[2] else pack(take('lm_head.weight'))).data_ptr()
+        # device bytes of the weights the step streams: projection images (fp8: with their scales), lm_head image, embedding
+        self.weight_bytes = {'projections': proj_bytes, 'lm_head': self._img_bytes - proj_bytes,
+                             'embed': self.embed.numel() * self.embed.element_size()}
         w.final_norm = dev(take('model.norm.weight')).data_ptr()
         w.rope_cos, w.rope_sin = self.rope_cos.data_ptr(), self.rope_sin.data_ptr()
         w.layers = C.cast(layers, C.POINTER(_lib.LlamaLayerWeightsC))
@@ -487,6 +669,7 @@ class LlamaVerifyEngine(object):
         cfg.max_blocks = self.max_blocks
         cfg.sliding_window = int(getattr(shape, 'sliding_window', 0))
         cfg.kv_ring = int(self.kv_ring)
+        cfg.weight_format = 1 if w8 else 0
         self._cfg = cfg
         nbytes = self._lib.la_llama_workspace_bytes(C.byref(cfg))
         if nbytes <= 0:

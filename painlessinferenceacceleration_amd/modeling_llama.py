@@ -13,12 +13,14 @@ from .pretrained_model import LookaheadPreTrainedModel
 
 class LlamaForCausalLM(LookaheadPreTrainedModel):
     def __init__(self, shape, state_dict, max_length=2048, device='cuda:0', eos_token_id=2, pad_token_id=0,
-                 attn_split=0, gemm_cfg=None, consume_state_dict=False, balanced=True, fuse=0, max_blocks=0, kv_ring=False, dtype=None):
+                 attn_split=0, gemm_cfg=None, consume_state_dict=False, balanced=True, fuse=0, max_blocks=0, kv_ring=False, dtype=None,
+                 weight_format=None):
         self.shape = shape
+        # weight_format='fp8': W8A16 projections (LlamaVerifyEngine); a state dict of float8_e4m3fn projections selects it by itself
         self.engine = LlamaVerifyEngine(shape, state_dict, max_length=max_length, device=device,
                                         attn_split=attn_split, gemm_cfg=gemm_cfg,
                                         consume_state_dict=consume_state_dict, balanced=balanced, fuse=fuse,
-                                        max_blocks=max_blocks, kv_ring=kv_ring, dtype=dtype)
+                                        max_blocks=max_blocks, kv_ring=kv_ring, dtype=dtype, weight_format=weight_format)
         self.generation_config = SimpleNamespace(eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                                  return_dict_in_generate=False)
         self.config = SimpleNamespace(is_encoder_decoder=False, vocab_size=shape.vocab)

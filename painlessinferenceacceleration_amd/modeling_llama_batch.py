@@ -13,7 +13,12 @@ from .pretrained_model_batch import LookaheadPreTrainedModel
 
 class LlamaForCausalLM(LookaheadPreTrainedModel):
     def __init__(self, shape, state_dict, max_length=2048, max_batch=8, device='cuda:0', eos_token_id=2, pad_token_id=0,
-                 attn_split=0, gemm_cfg=None, consume_state_dict=False, balanced=True, max_blocks=None, kv_ring=False, dtype=None):
+                 attn_split=0, gemm_cfg=None, consume_state_dict=False, balanced=True, max_blocks=None, kv_ring=False, dtype=None,
+                 weight_format=None):
+        if weight_format is not None:
+            # the batch path runs the multi-block step, which has no fp8 launch (the single-sequence LlamaForCausalLM has)
+            raise ValueError(f'weight_format={weight_format!r}: the batch models run the multi-block step, which has 16-bit weights only; '
+                             'fp8 weights run on the single-sequence models (modeling_llama.LlamaForCausalLM, Qwen2ForCausalLM)')
         self.shape = shape
         self.engine = LlamaVerifyEngine(shape, state_dict, max_length=max_length, device=device, attn_split=attn_split,
                                         gemm_cfg=gemm_cfg, consume_state_dict=consume_state_dict, balanced=balanced,
