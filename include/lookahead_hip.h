@@ -43,7 +43,7 @@ extern "C" {
 #define LA_MOE_MAX_E      8   /* experts per mixture-of-experts layer (Mixtral: 8, top-2) */
 
 /* ABI version: bumped when a signature changes. */
-#define LA_ABI_VERSION  14   /* bumped whenever a struct layout or an entry point changes */
+#define LA_ABI_VERSION  15   /* bumped whenever a struct layout or an entry point changes */
 int          la_abi_version(void);   /* == LA_ABI_VERSION of the header the library was built from */
 /* Storage / MFMA-input type of the loaded library: 0 = bfloat16 (liblookahead_hip.so), 1 = float16 (liblookahead_hip_f16.so, the
  * dtype the reference's examples and benchmarks run, lookahead/benchmarks/llama_benchmark.py:27).  The two libraries are the same
@@ -494,7 +494,8 @@ int la_llama_step_eager(la_llama* m, void* stream, const int32_t* host_in, int32
 /* Device addresses of internal buffers for parity tests: 0 logits bf16 [64][vocab], 1 state,
  * 2 hidden h bf16 [64][hidden], 3 final normed x (packed), 4/5 main K/V cache, 6/7 fresh K/V tiles,
  * 8 batch state block (LA_BST_*), 9 routing weights fp32 [n_layers][64][LA_MOE_MAX_E] of the last block, 10 accumulated
- * expert output bf16 [64][hidden] of the last MoE layer. */
+ * expert output bf16 [64][hidden] of the last MoE layer, 11-14 the multi-block twins (logits, LA_MOUT_* block, hidden, routing
+ * weights), 15 the repetition-penalty context bitmaps uint32 [n_slots][vocab / 32]. */
 void* la_llama_buffer(la_llama* m, int which);
 /* Kernel-class timing of one block with HIP events recorded on `stream` between eager launches
  * (bench.py's roofline block).  out_ms[0..6] = per-step time summed over the launches of
@@ -508,10 +509,39 @@ int la_llama_profile(la_llama* m, void* stream, const int32_t* host_in, int iter
  * `roofline.achieved`; the rocprofv3 kernel average under profiles/ is the cross-check. */
 int la_llama_profile_gateup(la_llama* m, void* stream, int iters, float* out_ms);
 
+/* ---- repetition penalty on the device -------------------------------------------------------------------------------------------
+ * transformers' RepetitionPenaltyLogitsProcessor (score < 0 ? score * penalty : score / penalty on every token of the context) as a
+ * stage of the verify step: between lm_head and the accept walk one workgroup per live tree row takes the PENALISED argmax of its row
+ * of logits, with the context = the slot's context set + the tokens on the row's root path (the set bits of its ancestor mask) — the
+ * context the reference's sequential walk (pretrained_model.py:825-875 with a non-empty processor list; batch twin
+ * pretrained_model_batch.py:814-875) would hand the processor if it reached that row, known BEFORE the walk because the penalty
+ * needs set membership only.  The accept walk, the commit and the result blocks are unchanged, so la_llama_step (graph and eager),
+ * la_lookahead_decode, la_llama_bstep and la_llama_mstep (mode 0 and mode 1; not wide trees: LA_E_ARG) keep their contracts and emit
+ * what the host walk emits.  Arithmetic: the stored 16-bit logit widened to fp32, multiplied or (IEEE) divided by float32(penalty),
+ * rounded to nearest-even back to the storage type, lowest index among equal maxima — torch's, bit for bit.
+ *   la_llama_set_repetition_penalty   per model; 1.0 = off (the default: a step then launches exactly what it launched before this
+ *                                     stage existed).  Synchronises `stream`; switching the stage on or off drops the model's captured
+ *                                     graphs (the next step captures again), a new value does not.
+ *   la_llama_penalty_seed             the context set of `slot` (slot 0 = the single-sequence step) := set(tokens): what the processor
+ *                                     sees at the first pick — the prompt; in the batch loops the left-PADDED row, pads included.  The
+ *                                     steps keep the set current on the device: every token a step emits is OR-ed in by that step.
+ *                                     A prefill chain (mode 1) emits too, so seed a slot after every pass of its prompt but the last
+ *                                     (before the pass that holds the prompt's last row).  la_llama_reset / la_llama_reset_slot clear.
+ *   la_llama_penalty_launches         steps launched with the stage since la_llama_create (tests: stays 0 while the penalty is off).
+ *   la_penalty_argmax / _transform    the row stage / the value transform alone (unit parity): logits [n_rows <= 64][vocab] of the
+ *                                     library's 16-bit type, one context bitmap [vocab / 32], ids / ancestor masks of the rows,
+ *                                     *d_penalty a device float -> d_argmax[n_rows]; transform: d_out[i] = penalised d_x[i]. */
+int la_llama_set_repetition_penalty(la_llama* m, void* stream, float penalty);
+int la_llama_penalty_seed(la_llama* m, void* stream, int slot, const int32_t* tokens, int n);
+int la_llama_penalty_launches(la_llama* m);
+int la_penalty_argmax(void* stream, const void* d_logits, int vocab, int n_rows, const uint32_t* d_bitmap, const int32_t* d_ids,
+                      const uint64_t* d_rowmask, const float* d_penalty, int32_t* d_argmax);
+int la_penalty_transform(void* stream, const void* d_x, int n, const float* d_penalty, void* d_out);
+
 /* ---- native decode loop: the per-step host work of lookahead_generation (pretrained_model.py:1172-1240) without the
  * interpreter: hier_get(last max_query_length tokens) -> la_llama_step -> stream_put, until max_length / eos / max_steps.
- * Greedy, empty logits-processor list, decoding_mode hier.  The prompt must already be prefilled (seq[0..seq_len) holds
- * prompt + first generated token, its trie `put` done).  Appends tokens to seq (capacity >= max_length + 16), fills
+ * Greedy, empty logits-processor list (or the device repetition penalty: la_llama_set_repetition_penalty), decoding_mode
+ * hier.  The prompt must already be prefilled (seq[0..seq_len) holds prompt + first generated token, its trie `put` done).  Appends tokens to seq (capacity >= max_length + 16), fills
  * dls/edls (capacity >= max_steps) and returns the number of steps in *n_steps; *finished = 1 when a stop condition
  * other than max_steps ended the loop.  host_in / host_out: pinned staging blocks (LA_IN_WORDS / LA_ST_OUTTOK+64). */
 typedef struct la_decode_params {

@@ -19,7 +19,7 @@ LIB_PATH_F16 = LAB_PATH_F16 if LAB_BUILD else os.path.join(_HERE, "liblookahead_
 LA_DTYPE_BF16, LA_DTYPE_F16 = 0, 1
 
 LA_OK = 0
-ABI_VERSION = 14        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
+ABI_VERSION = 15        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
 LA_MODE_INPUT, LA_MODE_OUTPUT, LA_MODE_MIX = 0, 1, 2
 LA_TREE_MAX = 64
 LA_MOE_MAX_E = 8
@@ -242,6 +242,11 @@ PROTOTYPES = {
     "la_mb_gemm_bias": (i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp),
     "la_llama_bstep_eager": (i32, vp, vp, vp, vp),
     "la_llama_reset_slot": (i32, vp, vp, i32),
+    "la_llama_set_repetition_penalty": (i32, vp, vp, f32),
+    "la_llama_penalty_seed": (i32, vp, vp, i32, pi32, i32),
+    "la_llama_penalty_launches": (i32, vp),
+    "la_penalty_argmax": (i32, vp, vp, i32, i32, vp, vp, vp, vp, vp),
+    "la_penalty_transform": (i32, vp, vp, i32, vp, vp),
 }
 
 # the kernel lab (include/lookahead_hip_lab.h): measurement knobs / A/B switches for scripts/ and the bitwise-identity tests — not part

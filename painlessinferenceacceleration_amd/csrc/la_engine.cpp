@@ -83,6 +83,13 @@ struct la_llama {
     // step (k_pf_only launches under the latency-bound kernels), and the two events that fork / join it
     hipStream_t pf_stream = nullptr;
     hipEvent_t pf_fork = nullptr, pf_join = nullptr;
+    // repetition penalty on the device (la_penalty.hip): per-slot context bitmaps [n_slots][vocab / 32], the penalty as a device word
+    // (the captured graphs read it: a new VALUE needs no capture, switching the stage on / off does), and how many steps ran the stage
+    unsigned* pen_bits = nullptr;
+    float* pen_val = nullptr;
+    float penalty = 1.0f;
+    bool pen_on = false;
+    int pen_launches = 0;
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -251,6 +258,8 @@ static size_t carve(la_llama* m, char* base) {
         m->mb_moe_cnt = cv.take<int>(2 * LA_MOE_MAX_E);
         m->mb_xg = cv.take<uint16_t>(E ? E * R * c.hidden : 8);
     }
+    m->pen_bits = cv.take<unsigned>((size_t)m->n_slots * (c.vocab / 32));
+    m->pen_val = cv.take<float>(64);
     return align_up(cv.off, 256);
 }
 
@@ -380,6 +389,7 @@ extern "C" int la_llama_reset(la_llama* m, void* stream) {
     int mk = m->cfg.max_keys;
     HIPCHK(hipMemcpyAsync(m->state + LA_ST_MAXKEYS, &mk, sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(m->bstate, 0, LA_BST_WORDS * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(m->pen_bits, 0, (size_t)m->n_slots * (m->cfg.vocab / 32) * sizeof(unsigned), st));
     HIPCHK(hipStreamSynchronize(st));
     m->seq_expected = 0;
     if (m->zc_out) m->zc_out[LA_ST_SEQ] = 0;
@@ -391,6 +401,9 @@ extern "C" int la_llama_reset_slot(la_llama* m, void* stream, int slot) {
     hipStream_t st = (hipStream_t)stream;
     if (slot < 0) HIPCHK(hipMemsetAsync(m->bstate, 0, LA_BST_WORDS * sizeof(int), st));
     else HIPCHK(hipMemsetAsync(m->bstate + LA_BST_NKEYS + slot, 0, sizeof(int), st));
+    const size_t pen_words = (size_t)(m->cfg.vocab / 32);
+    if (slot < 0) HIPCHK(hipMemsetAsync(m->pen_bits, 0, (size_t)m->n_slots * pen_words * sizeof(unsigned), st));
+    else HIPCHK(hipMemsetAsync(m->pen_bits + (size_t)slot * pen_words, 0, pen_words * sizeof(unsigned), st));
     HIPCHK(hipStreamSynchronize(st));
     return LA_OK;
 }
@@ -647,10 +660,19 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
     }
     P(KC_LMHEAD);
     int* am_rows = batch ? m->bstate + LA_BST_ARGMAX : m->state + LA_ST_ARGMAX;
+    // repetition penalty (la_penalty.hip): the penalised argmax of every live row over the logits lm_head has just written takes the
+    // place of the candidate reduction, the walk kernels run as they are, then the emitted tokens join the slot's context set
+    const bool pen = m->pen_on;
+    PenArgs pa{};
+    if (pen) {
+        pa.kind = batch ? LA_PEN_BATCH : LA_PEN_SINGLE; pa.vocab = c.vocab; pa.n_slots = m->n_slots; pa.nblk = 1;
+        pa.logits = m->logits; pa.bitmaps = m->pen_bits; pa.penalty = m->pen_val; pa.ids = m->ids;
+        pa.rowmask = (const unsigned long long*)m->rowmask; pa.state = batch ? m->bstate : m->state; pa.in = m->bin; pa.out = am_rows;
+    }
     if (c.balanced_wg[2] > 0) {
         KCHK(lk_gemm64r_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, c.balanced_wg[2], m->logits, m->cand_val, m->cand_idx));
         P(KC_OTHER);
-        if (!batch && !g_la_split_head_tail) {
+        if (!pen && !batch && !g_la_split_head_tail) {
             // argmax finalize + accept walk + result hand-over in ONE launch, the KV commit after it: the host reads the accepted
             // tokens (and starts its trie update / next query) while the commit kernel still runs
             KCHK(lk_step_tail(st, m->cand_val, m->cand_idx, c.balanced_wg[2], m->ids, m->rowmask, m->state, (int*)zc_out));
@@ -658,17 +680,20 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
             P(KC_N);
             return join_pf();
         }
-        KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, c.balanced_wg[2], am_rows));
+        if (!pen) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, c.balanced_wg[2], am_rows));
     } else {
         KCHK(lk_gemm64_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, m->lm_rb, m->logits, m->cand_val, m->cand_idx));
         P(KC_OTHER);
-        KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, lk_logits_cand_slots(c.vocab, m->lm_rb), am_rows));
+        if (!pen) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, lk_logits_cand_slots(c.vocab, m->lm_rb), am_rows));
     }
+    if (pen) KCHK(lk_pen_argmax(st, pa));
     if (batch) {
         KCHK(lk_accept_scan_b(st, m->bin, m->ids, m->rowmask, m->bstate, m->n_slots, c.max_keys, ring));
+        if (pen) KCHK(lk_pen_update(st, pa));
         KCHK(lk_kv_commit_b(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->bstate, c.n_layers, c.n_kv_heads, m->total_keys));
     } else {
         KCHK(lk_accept_scan(st, m->ids, m->rowmask, m->state));
+        if (pen) KCHK(lk_pen_update(st, pa));
         KCHK(lk_kv_commit(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->state, c.n_layers, c.n_kv_heads, m->total_keys, ring));
         if (zc_out) KCHK(lk_publish(st, m->state, (int*)zc_out));
     }
@@ -721,6 +746,7 @@ static int bstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     int v = 0, bsplit = m->nsplit;
     const int target = m->nsplit / active > 1 ? m->nsplit / active : 1;
     while (v < 3 && bsplit > target && bsplit % 2 == 0) { bsplit /= 2; ++v; }
+    if (m->pen_on) ++m->pen_launches;
     if (eager) {
         int rc = enqueue_step(m, st, nullptr, true, nullptr, nullptr, bsplit);
         if (rc != LA_OK) return rc;
@@ -760,6 +786,7 @@ static int mb_split(int nblk, int n_heads = 32, int cus = 256) {
 static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = false) {
     const la_llama_config& c = m->cfg;
     if (!m->qkv_fused) { la_set_error("mstep needs the fused QKV image (gemm_cfg[1] >= 0)"); return LA_E_ARG; }
+    if (m->pen_on && wide) { la_set_error("mstep: the device repetition penalty has no wide-tree form (la_llama_set_repetition_penalty(1.0) + host walk)"); return LA_E_ARG; }
     const int M = nblk * 64;
     const int npass_rows = (nblk <= 2 ? nblk : ((nblk + 3) / 4) * 4) * 64;     // rows whole passes write (slab stride)
     // la_debug_set key 12 (measurement, off by default): at >= 5 blocks the slab GEMMs of a dense model run 2 K splits over 4 token
@@ -857,8 +884,16 @@ static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = fals
     MbGemm h{}; h.wp = m->w.lm_head; h.xp = m->mb_xp; h.N = c.vocab; h.K = c.hidden; h.nblk = nblk; h.n_wg = c.balanced_wg[2]; h.ksplit = 1;
     h.logits = m->mb_logits; h.cand_val = m->mb_cand_val; h.cand_idx = m->mb_cand_idx;
     KCHK(lk_mb_gemm(st, 3, h));
+    PenArgs pa{};
+    if (m->pen_on) {
+        pa.kind = LA_PEN_MBLOCK; pa.vocab = c.vocab; pa.n_slots = m->n_slots; pa.nblk = nblk;
+        pa.logits = m->mb_logits; pa.bitmaps = m->pen_bits; pa.penalty = m->pen_val; pa.ids = m->mb_ids;
+        pa.rowmask = (const unsigned long long*)m->mb_rowmask; pa.state = m->mb_out; pa.meta = m->mb_meta; pa.out = m->mb_out + LA_MOUT_ARGMAX;
+        KCHK(lk_pen_argmax(st, pa));
+    } else
     KCHK(lk_mb_argmax(st, m->mb_cand_val, m->mb_cand_idx, lk_mb_cand_slots(lwg), nblk, m->mb_out + LA_MOUT_ARGMAX));
     KCHK(lk_mb_accept_scan(st, m->mb_meta, m->mb_ids, m->mb_rowmask, (const uint64_t*)(m->mb_in + LA_MIN_XMASK), m->mb_out + LA_MOUT_ARGMAX, nblk, c.max_keys, c.kv_ring ? 1 : 0, m->bstate, m->mb_out));
+    if (m->pen_on) KCHK(lk_pen_update(st, pa));
     KCHK(lk_mb_kv_commit(st, m->mb_kfresh, m->mb_vfresh, m->kmain, m->vmain, m->mb_out, nblk, c.n_layers, c.n_kv_heads, m->total_keys));
     return LA_OK;
 }
@@ -872,6 +907,7 @@ static int mstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     const int gi = (wide ? LA_MB_MAX + 1 : 0) + nblk;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(m->mb_in, host_in, LA_MIN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
+    if (m->pen_on) ++m->pen_launches;
     if (eager) {
         int rc = enqueue_mstep(m, st, nblk, wide);
         if (rc != LA_OK) return rc;
@@ -905,6 +941,7 @@ extern "C" int la_llama_mstep_trie(la_llama* m, void* stream, int nblk, const in
     for (int b = 0; b < nblk; ++b) if (slots[b] < 0 || slots[b] >= m->n_slots) return LA_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     KCHK(lk_mb_fill_from_trie(st, d_ids, d_rowmask, d_n, slots, limits, last_tok, nblk, m->mb_in));
+    if (m->pen_on) ++m->pen_launches;
     const int gi = nblk;
     if (m->mready[gi] && m->mepoch[gi] != g_la_graph_epoch) {
         (void)hipGraphExecDestroy(m->mgraphs[gi]);
@@ -975,6 +1012,7 @@ extern "C" int la_llama_step(la_llama* m, void* stream, const int32_t* host_in, 
         }
     }
     m->seq_expected += 1;
+    if (m->pen_on) ++m->pen_launches;
     HIPCHK(hipGraphLaunch(long_ctx ? m->graph_long : m->graph_exec, st));
     return LA_OK;
 }
@@ -1001,6 +1039,7 @@ extern "C" int la_llama_step_eager(la_llama* m, void* stream, const int32_t* hos
     if (!m || !host_in) return LA_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(m->in, host_in, LA_IN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
+    if (m->pen_on) ++m->pen_launches;
     int rc = enqueue_step(m, st, nullptr, false, nullptr, nullptr, 0, host_in[LA_IN_NKEYS_HINT] + LA_TREE_MAX > m->attn_thr);
     if (rc != LA_OK) return rc;
     if (host_out)
@@ -1188,6 +1227,66 @@ extern "C" int la_llama_set_nkeys(la_llama* m, void* stream, int slot, int nkeys
     return LA_OK;
 }
 
+// ---- repetition penalty on the device (la_penalty.hip) -----------------------------------------------------------------
+// every captured graph of the model holds the step WITH or WITHOUT the penalty stage: switching it on / off drops them (the next
+// step captures again, as after a g_la_graph_epoch change); a new value only rewrites the device word the stage reads
+static void drop_graphs(la_llama* m) {
+    if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
+    if (m->graph_long) (void)hipGraphExecDestroy(m->graph_long);
+    m->graph_exec = m->graph_long = nullptr;
+    m->graph_ready = m->graph_long_ready = false;
+    for (int i = 0; i < 4; ++i) if (m->bready[i]) { (void)hipGraphExecDestroy(m->bgraphs[i]); m->bgraphs[i] = nullptr; m->bready[i] = false; }
+    for (int i = 0; i < 2 * (LA_MB_MAX + 1); ++i) if (m->mready[i]) { (void)hipGraphExecDestroy(m->mgraphs[i]); m->mgraphs[i] = nullptr; m->mready[i] = false; }
+}
+
+extern "C" int la_llama_set_repetition_penalty(la_llama* m, void* stream, float penalty) {
+    if (!m || !(penalty > 0.f) || !(penalty <= 3.0e38f)) { la_set_error("repetition penalty must be a finite float > 0 (1.0 = off)"); return LA_E_ARG; }
+    const bool on = penalty != 1.0f;
+    if (on && lk_pen_lds_bytes(m->cfg.vocab) > 64 * 1024) { la_set_error("repetition penalty: the context bitmap of this vocabulary does not fit the LDS"); return LA_E_RANGE; }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(st));                       // no step in flight reads the word / runs a graph that is dropped below
+    HIPCHK(hipMemcpyAsync(m->pen_val, &penalty, sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (on != m->pen_on) drop_graphs(m);
+    m->penalty = penalty;
+    m->pen_on = on;
+    return LA_OK;
+}
+
+extern "C" int la_llama_penalty_seed(la_llama* m, void* stream, int slot, const int32_t* tokens, int n) {
+    if (!m || slot < 0 || slot >= m->n_slots || n < 0 || (n > 0 && !tokens)) return LA_E_ARG;
+    const size_t words = (size_t)(m->cfg.vocab / 32);
+    std::vector<unsigned> bits(words, 0u);
+    for (int i = 0; i < n; ++i) {
+        if (tokens[i] < 0 || tokens[i] >= m->cfg.vocab) { la_set_error("penalty_seed: token outside the vocabulary"); return LA_E_RANGE; }
+        bits[tokens[i] >> 5] |= 1u << (tokens[i] & 31);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(m->pen_bits + (size_t)slot * words, bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));       // bits lives on this stack frame
+    return LA_OK;
+}
+
+extern "C" int la_llama_penalty_launches(la_llama* m) { return m ? m->pen_launches : LA_E_ARG; }
+
+extern "C" int la_penalty_argmax(void* stream, const void* d_logits, int vocab, int n_rows, const uint32_t* d_bitmap, const int32_t* d_ids,
+                                 const uint64_t* d_rowmask, const float* d_penalty, int32_t* d_argmax) {
+    if (!d_logits || !d_bitmap || !d_ids || !d_rowmask || !d_penalty || !d_argmax || n_rows < 1 || n_rows > LA_TREE_MAX || vocab <= 0 ||
+        (vocab & 31) || lk_pen_lds_bytes(vocab) > 64 * 1024) return LA_E_ARG;
+    PenArgs pa{};
+    pa.kind = LA_PEN_ROWS; pa.vocab = vocab; pa.n_slots = 1; pa.nblk = 1; pa.n_rows = n_rows;
+    pa.logits = d_logits; pa.bitmaps = (unsigned*)d_bitmap; pa.penalty = d_penalty; pa.ids = d_ids;
+    pa.rowmask = (const unsigned long long*)d_rowmask; pa.out = d_argmax;
+    KCHK(lk_pen_argmax((hipStream_t)stream, pa));
+    return LA_OK;
+}
+
+extern "C" int la_penalty_transform(void* stream, const void* d_x, int n, const float* d_penalty, void* d_out) {
+    if (!d_x || !d_penalty || !d_out || n < 0) return LA_E_ARG;
+    KCHK(lk_pen_transform((hipStream_t)stream, d_x, n, d_penalty, d_out));
+    return LA_OK;
+}
+
 extern "C" void* la_llama_buffer(la_llama* m, int which) {
     if (!m) return nullptr;
     switch (which) {
@@ -1206,6 +1305,7 @@ extern "C" void* la_llama_buffer(la_llama* m, int which) {
         case 12: return m->mb_max ? m->mb_out : nullptr;
         case 13: return m->mb_max ? m->mb_h : nullptr;
         case 14: return m->mb_max ? m->mb_route_w : nullptr;
+        case 15: return m->pen_bits;
         default: return nullptr;
     }
 }

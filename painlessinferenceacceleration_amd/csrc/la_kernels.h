@@ -153,3 +153,23 @@ int lk_trie_hier_get2(hipStream_t st, const int* tok, const double* fo, const do
                       int decoding_length, int branch_length, int min_in, int min_out, int mode, const int* stop, int n_stop,
                       int* scratch_q, double* scratch_v, int* out_ids, uint64_t* out_rowmask, int* out_n, int* out_sizes,
                       int* out_nsizes);
+
+// ---- repetition penalty on the device (la_penalty.hip): the penalised argmax of every live tree row + the context-set update
+enum { LA_PEN_SINGLE = 0, LA_PEN_BATCH = 1, LA_PEN_MBLOCK = 2, LA_PEN_ROWS = 3 };
+struct PenArgs {
+    int kind;                         // which step form lays the rows out (LA_PEN_*); LA_PEN_ROWS: n_rows plain rows of slot 0 (unit entry)
+    int vocab, n_slots, nblk, n_rows;
+    const void* logits;               // [rows][vocab] in the storage type, as lm_head wrote them
+    unsigned* bitmaps;                // [n_slots][vocab / 32] context sets
+    const float* penalty;             // device word: float32(penalty)
+    const int* ids;                   // tree tokens / ancestor masks of the step (block-row or own-block indices)
+    const unsigned long long* rowmask;
+    const int* state;                 // SINGLE: LA_ST_* block; BATCH: LA_BST_* block; MBLOCK: the LA_MOUT_* block (update only)
+    const int* in;                    // BATCH: LA_BIN_* block (per-slot modes)
+    const int* meta;                  // MBLOCK: block meta records (LA_MBM_*)
+    int* out;                         // argmax word of every row
+};
+size_t lk_pen_lds_bytes(int vocab);
+int lk_pen_argmax(hipStream_t st, const PenArgs& a);
+int lk_pen_update(hipStream_t st, const PenArgs& a);
+int lk_pen_transform(hipStream_t st, const void* x, int n, const float* d_penalty, void* out);

@@ -697,6 +697,8 @@ class LlamaVerifyEngine(object):
             self._min_xm = self._min_np[_lib.LA_MIN_XMASK:_lib.LA_MIN_XMASK + 2 * 3 * 64 * _lib.LA_MB_MAX].view(np.uint64).reshape(_lib.LA_MB_MAX * 64, 3)
         self.slot_keys = [0] * self.n_slots
         self.n_keys = 0
+        self.repetition_penalty = 1.0
+        self._pen_ctx = {}
         self.reset()
 
     def __del__(self):
@@ -717,14 +719,54 @@ class LlamaVerifyEngine(object):
         check(self._lib.la_llama_reset(self._h, self._sp()), 'llama_reset')
         self.n_keys = 0
         self.slot_keys = [0] * self.n_slots
+        self._pen_ctx = {}
+
+    # ---- repetition penalty on the device (csrc/la_penalty.hip) -------------------------------------------------------------
+    def set_repetition_penalty(self, penalty):
+        """transformers' RepetitionPenaltyLogitsProcessor(penalty) as a stage of every verify step (step / decode_native / bstep /
+        mstep, first token after a prefill included): the penalised argmax of every live tree row is taken on the device and the
+        fused accept walk runs on it, emitting what the host walk over verify_only + commit emits.  1.0 = off (the default: the
+        steps launch exactly what they launch without this stage).  The context set of a slot is seeded by prefill / bprefill /
+        mprefill (the prompt, or what seed_penalty_context recorded for the slot) and kept current on the device afterwards."""
+        penalty = float(penalty)
+        check(self._lib.la_llama_set_repetition_penalty(self._h, self._sp(), penalty), 'set_repetition_penalty')
+        self.repetition_penalty = penalty
+
+    def seed_penalty_context(self, slot, tokens):
+        """The context set of `slot` := set(tokens), now, and again from the same tokens when the slot's next prefill reaches the
+        pass that holds the prompt's last row (a prefill chain emits a token per pass; only the last one is read).  The batch loops
+        hand the left-padded row here, pads included: that is what the reference's walk hands the processor."""
+        tokens = [int(x) for x in tokens]
+        self._pen_ctx[int(slot)] = tokens
+        self._pen_seed(int(slot), tokens)
+
+    def _pen_seed(self, slot, tokens):
+        arr = np.ascontiguousarray(tokens, dtype=np.int32)
+        check(self._lib.la_llama_penalty_seed(self._h, self._sp(), int(slot), arr.ctypes.data_as(_lib.pi32), len(arr)), 'penalty_seed')
+
+    def _pen_seed_final(self, slot, prompt_ids):
+        """before the prefill pass that holds the last row of `slot`'s prompt (no-op while the penalty is off)"""
+        if self.repetition_penalty != 1.0:
+            self._pen_seed(slot, self._pen_ctx.pop(slot, prompt_ids))
+
+    def penalty_launches(self):
+        """steps launched with the penalty stage since the engine was created"""
+        return int(self._lib.la_llama_penalty_launches(self._h))
+
+    def penalty_context(self, slot=0):
+        """uint32 [vocab / 32]: the context bitmap of `slot` (bit t of word t // 32 <=> token t is in the set)"""
+        words = self.shape.vocab // 32
+        return self._view(15, self.n_slots * words * 4, torch.int32).view(self.n_slots, words)[slot]
 
     # ---- cursor batch ------------------------------------------------------------------------------------
     def reset_slot(self, slot):
         check(self._lib.la_llama_reset_slot(self._h, self._sp(), int(slot)), 'reset_slot')
         if slot < 0:
             self.slot_keys = [0] * self.n_slots
+            self._pen_ctx = {}
         else:
             self.slot_keys[slot] = 0
+            self._pen_ctx.pop(slot, None)
 
     def bstep(self, segments, eager=False):
         """One verify block shared by several sequences.  segments: list of (slot, ids, local_rowmask, mode, limit);
@@ -801,6 +843,8 @@ class LlamaVerifyEngine(object):
         tok = None
         for s in range(0, len(prompt_ids), 64):
             blk = prompt_ids[s:s + 64]
+            if s + 64 >= len(prompt_ids):
+                self._pen_seed_final(slot, prompt_ids)
             tok = self.bstep([(slot, np.asarray(blk, dtype=np.int32), self._CHAIN[:len(blk)], 1, 1)], eager=eager)[slot][0]
         return tok
 
@@ -821,6 +865,8 @@ class LlamaVerifyEngine(object):
                 segments.append((s, np.asarray(todo[s][done[s]:done[s] + n], dtype=np.int32), self._CHAIN[:n], 1, 1))
                 done[s] += n
                 room -= n
+                if done[s] == len(todo[s]):
+                    self._pen_seed_final(s, todo[s])
             out = self.bstep(segments, eager=eager)
             for s, _, _, _, _ in segments:
                 if done[s] == len(todo[s]):
@@ -1056,6 +1102,8 @@ class LlamaVerifyEngine(object):
             piece = prompt_ids[s:s + per]
             blocks = [(slot, np.asarray(piece[i:i + 64], dtype=np.int32), self._CHAIN[:len(piece[i:i + 64])], 1, 1)
                       for i in range(0, len(piece), 64)]
+            if s + per >= len(prompt_ids):
+                self._pen_seed_final(slot, prompt_ids)
             tok = self.mstep(blocks, eager=eager)[-1][0]
         if slot == 0:
             check(self._lib.la_llama_set_nkeys(self._h, self._sp(), 0, self.slot_keys[0]), 'set_nkeys')
@@ -1076,6 +1124,9 @@ class LlamaVerifyEngine(object):
         first = {}
         for i in range(0, len(pieces), self.max_blocks):
             group = pieces[i:i + self.max_blocks]
+            for s, _, last in group:
+                if last:
+                    self._pen_seed_final(s, todo[s])
             out = self.mstep([(s, np.asarray(pc, dtype=np.int32), self._CHAIN[:len(pc)], 1, 1) for s, pc, _ in group], eager=eager)
             for (s, _, last), toks in zip(group, out):
                 if last:
@@ -1197,6 +1248,8 @@ class LlamaVerifyEngine(object):
         tok = None
         for s in range(0, len(prompt_ids), 64):
             blk = prompt_ids[s:s + 64]
+            if s + 64 >= len(prompt_ids):
+                self._pen_seed_final(0, prompt_ids)
             toks, _ = self.step(np.asarray(blk, dtype=np.int32), self._CHAIN[:len(blk)], mode=1, eager=eager)
             tok = toks[0]
         return tok

@@ -48,6 +48,28 @@ class LookaheadDecoderOnlyOutput(object):
     kwargs: Dict[str, Any] = field(default_factory=dict)
 
 
+def device_repetition_penalty(logits_processor, engine, do_sample=False, enabled=True):
+    """The penalty value when the processor list can run as the engine's device stage (LlamaVerifyEngine.set_repetition_penalty), else
+    None (-> the host walk).  The list must be exactly ONE transformers RepetitionPenaltyLogitsProcessor — the exact type, not a
+    subclass (a subclass may override __call__) — whose optional attributes are at their defaults, so that `penalty` is its whole
+    state; greedy decoding; an engine that has the stage (the oracle-backed CPU engines of the tests do not); and `enabled`
+    (decoding_kwargs['device_processors'], default True: False is the A/B switch and escape hatch)."""
+    if not enabled or do_sample or logits_processor is None or len(logits_processor) != 1:
+        return None
+    if not hasattr(engine, 'set_repetition_penalty'):
+        return None
+    from transformers import RepetitionPenaltyLogitsProcessor
+    proc = logits_processor[0]
+    if type(proc) is not RepetitionPenaltyLogitsProcessor:
+        return None
+    if any(getattr(proc, name, None) is not None for name in ('prompt_ignore_length', 'logits_indices', 'cu_seq_lens_q')):
+        return None
+    penalty = getattr(proc, 'penalty', None)
+    if not isinstance(penalty, float) or not penalty > 0:
+        return None
+    return penalty
+
+
 # ---------------------------------------------------------------------------------------------------- generate() front door
 _GEN_FIELDS = ('max_length', 'max_new_tokens', 'min_length', 'min_new_tokens', 'eos_token_id', 'pad_token_id', 'do_sample',
                'repetition_penalty', 'no_repeat_ngram_size', 'bad_words_ids', 'temperature', 'top_k', 'top_p', 'max_time',

@@ -16,7 +16,8 @@ import torch
 
 from . import _lib
 from .lookahead_cache import LookaheadCache
-from .lookahead_generation_utils import GenerationMode, LookaheadDecoderOnlyOutput, resolve_generate_args
+from .lookahead_generation_utils import (GenerationMode, LookaheadDecoderOnlyOutput, device_repetition_penalty,
+                                          resolve_generate_args)
 
 _ONE = np.array([1], dtype=np.uint64)
 
@@ -267,6 +268,15 @@ class LookaheadPreTrainedModel(object):
         fresh_scores = scores is not None and bool(decoding_kwargs.get('fresh_scores', False))
         if fresh_scores:
             sequential = True            # the host walk sees every logits row it picks from
+        # a list that is exactly one RepetitionPenaltyLogitsProcessor runs as a stage of the device step (the penalised argmax of
+        # every tree row, then the fused accept walk: csrc/la_penalty.hip) and keeps the graph, the fused tail and the native loop;
+        # every other list, sampling, scores, wide trees, the device trie and sharded jobs keep the host walk below
+        dev_penalty = None
+        if sequential and scores is None and not wide and gather is None and not decoding_kwargs.get('device_trie', False):
+            dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample,
+                                                    enabled=decoding_kwargs.get('device_processors', True))
+        if dev_penalty is not None:
+            sequential = False
         native_loop = (not sequential and streamer is None and dm.split('_')[0] == 'hier' and not wide
                        and custom_stop is None and gather is None and scores is None
                        and not decoding_kwargs.get('device_trie', False)
@@ -291,6 +301,8 @@ class LookaheadPreTrainedModel(object):
         last_scores = None         # what the reference's model_kwargs['next_tokens_scores'] holds
         flushed = False
         try:
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(dev_penalty)      # prefill seeds the context set with the prompt
             while True:
                 if first:
                     host_row = sequential or scores is not None      # the last prompt row's logits must stay readable
@@ -400,6 +412,8 @@ class LookaheadPreTrainedModel(object):
                     flushed = True
                     break
         finally:
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(1.0)              # also after an exception: the next request starts without the stage
             # an exception mid-generation must not leave this request's stream buffer / input frequencies behind (they would
             # mix into the next request); the reference flushes on the normal path only (pretrained_model.py:1236-1239)
             if not flushed:
@@ -424,15 +438,19 @@ class LookaheadPreTrainedModel(object):
     # ---------------------------------------------------------------------------------- plain greedy (mode off)
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, eos_token_id=None, logits_processor=None, do_sample=False,
-                      stopping_criteria=None):
+                      stopping_criteria=None, device_processors=True):
         """Plain decoding through the same engine (T=1 blocks): the `use_lookahead=False` leg of the reference's
         examples (examples/llama_example.py:39-69).  With a processor list or sampling each token is picked on the host
-        from the block's logits row (forward-only step + commit)."""
+        from the block's logits row (forward-only step + commit) — except a list that is exactly one repetition penalty, which
+        runs as the device stage lookahead_generation uses (device_processors=False: the host pick)."""
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         seq = input_ids[0].tolist()
         eng = self.engine
         eng.reset()
         host_pick = do_sample or (logits_processor is not None and len(logits_processor) > 0)
+        dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample, enabled=device_processors) if host_pick else None
+        if dev_penalty is not None:
+            host_pick = False
         custom_stop = _custom_stop(stopping_criteria)        # the caller's criteria besides the length bound, once per token
 
         def pick(row):
@@ -444,19 +462,25 @@ class LookaheadPreTrainedModel(object):
                 return int(torch.multinomial(torch.softmax(scores.float(), dim=-1), num_samples=1)[0, 0])
             return int(torch.argmax(scores, dim=-1)[0])
 
-        tok = eng.prefill(seq, fast=False) if host_pick else eng.prefill(seq)
-        if host_pick:
-            tok = pick((len(seq) - 1) % 64)
-        seq.append(tok)
-        while len(seq) < max_length and tok not in eos and not (custom_stop is not None and custom_stop(seq, input_ids.device)):
+        try:
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(dev_penalty)
+            tok = eng.prefill(seq, fast=False) if host_pick else eng.prefill(seq)
             if host_pick:
-                eng.verify_only(np.asarray([tok], dtype=np.int32), _ONE)
-                tok = pick(0)
-                eng.commit([0])
-            else:
-                toks, _ = eng.step(np.asarray([tok], dtype=np.int32), _ONE, mode=0)
-                tok = toks[0]
+                tok = pick((len(seq) - 1) % 64)
             seq.append(tok)
+            while len(seq) < max_length and tok not in eos and not (custom_stop is not None and custom_stop(seq, input_ids.device)):
+                if host_pick:
+                    eng.verify_only(np.asarray([tok], dtype=np.int32), _ONE)
+                    tok = pick(0)
+                    eng.commit([0])
+                else:
+                    toks, _ = eng.step(np.asarray([tok], dtype=np.int32), _ONE, mode=0)
+                    tok = toks[0]
+                seq.append(tok)
+        finally:
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(1.0)
         return torch.tensor([seq], dtype=torch.long, device=input_ids.device)
 
     # ------------------------------------------------------------------------------------------- front door
@@ -504,7 +528,7 @@ class LookaheadPreTrainedModel(object):
         out = self.greedy_search(input_ids, ga.max_length, ga.eos_token_id if ga.eos_token_id is not None
                                  else getattr(self.generation_config, 'eos_token_id', None),
                                  logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
-                                 stopping_criteria=ga.stopping_criteria)
+                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True))
         return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out
 
     def stream_generate(self, *args, **kwargs):

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .lookahead_cache import LookaheadCache
-from .lookahead_generation_utils import LookaheadDecoderOnlyOutput, resolve_generate_args
+from .lookahead_generation_utils import LookaheadDecoderOnlyOutput, device_repetition_penalty, resolve_generate_args
 from .pretrained_model import _custom_stop, _max_length_of
 
 _ONE = np.array([1], dtype=np.uint64)
@@ -216,12 +216,29 @@ class LookaheadPreTrainedModel(object):
             for i in range(bs):                                                 # :1204-1207 (pads included, as there)
                 self.lookahead_cache.put(ids0[i, 1:-1].tolist(), branch_length=branch_length + 1, mode='input', idx=i)
         rows = [ids0[i].tolist() for i in range(bs)]      # padded-coordinate token rows; cursor = len(row) - 1
+        # a list that is exactly one RepetitionPenaltyLogitsProcessor runs as a stage of the device step (csrc/la_penalty.hip) and
+        # keeps the fused accept, the async multi-block step and overlap_trie_update; the reference's walk hands the processor
+        # input_ids[b, :cur + i + 2], left pads included, so every slot's context set is seeded with its PADDED row.  Other lists,
+        # sampling, scores, requests in which a sample's tree may be wider than one block, the device trie and sharded jobs keep
+        # the host walk.
+        dev_penalty = None
+        if sequential and scores is None and gather is None and not decoding_kwargs.get('device_trie', False) and \
+                min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX:
+            dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=bool(decoding_kwargs.get('do_sample', False)),
+                                                    enabled=decoding_kwargs.get('device_processors', True))
+        if dev_penalty is not None:
+            sequential = False
+            decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the penalty stage)
         finished_rows = [None] * bs
         batch_indices = list(range(bs))
         eos_set = set(eos_token_id) if eos_token_id is not None else set()
         try:
             ts = time.time()
             eng.reset_slot(-1)
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(dev_penalty)
+                for i in range(bs):
+                    eng.seed_penalty_context(i, ids0[i].tolist())
             # prefill: valid prompt tokens of every sample, packed into shared 64-row chain blocks
             prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
             multi = bool(getattr(eng, 'max_blocks', 0))
@@ -461,6 +478,9 @@ class LookaheadPreTrainedModel(object):
                 for i in range(bs):
                     self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=i)
             raise
+        finally:
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(1.0)          # also after an exception: the next request starts without the stage
         if streamer is not None:
             streamer.end()
         seqs = np.full((bs, max_cur + 1), pad, dtype=np.int64)
@@ -508,7 +528,7 @@ class LookaheadPreTrainedModel(object):
 
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, attention_mask=None, eos_token_id=None, pad_token_id=0,
-                      logits_processor=None, do_sample=False, stopping_criteria=None):
+                      logits_processor=None, do_sample=False, stopping_criteria=None, device_processors=True):
         """Plain decoding of the whole batch through the same engine (one row per sample per block).  With a processor list or
         sampling every token is picked on the host from the sample's logits row (forward-only step + la_llama_bcommit).
         `stopping_criteria`: the caller's criteria besides the length bound (MaxTimeCriteria, custom ones) are evaluated per
@@ -522,6 +542,24 @@ class LookaheadPreTrainedModel(object):
         prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
         host_pick = do_sample or (logits_processor is not None and len(logits_processor) > 0)
         multi = bool(getattr(eng, 'max_blocks', 0))
+        # exactly one repetition penalty: the device stage of lookahead_generation, every slot seeded with its padded row
+        dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample, enabled=device_processors) if host_pick else None
+        if dev_penalty is not None:
+            host_pick = False
+        try:
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(dev_penalty)
+                for i in range(bs):
+                    eng.seed_penalty_context(i, ids0[i].tolist())
+            return self._greedy_search(eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length,
+                                       eos, pad_token_id, input_ids.device)
+        finally:
+            if dev_penalty is not None:
+                eng.set_repetition_penalty(1.0)
+
+    def _greedy_search(self, eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length, eos,
+                       pad_token_id, out_device):
+        bs = ids0.shape[0]
 
         def pick(ctx_ids, row):
             scores = row[None]
@@ -548,7 +586,7 @@ class LookaheadPreTrainedModel(object):
 
         def alive(b):
             return len(rows[b]) < max_length and rows[b][-1] not in eos and \
-                not (custom_stop is not None and custom_stop(rows[b], input_ids.device))
+                not (custom_stop is not None and custom_stop(rows[b], out_device))
 
         live = [b for b in range(bs) if alive(b)]
         while live:
@@ -566,7 +604,7 @@ class LookaheadPreTrainedModel(object):
         seqs = np.full((bs, L), pad_token_id, dtype=np.int64)
         for b in range(bs):
             seqs[b, :len(rows[b])] = rows[b]
-        return torch.from_numpy(seqs).to(input_ids.device)
+        return torch.from_numpy(seqs).to(out_device)
 
     def generate(self, inputs=None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  prefix_allowed_tokens_fn=None, synced_gpus=None, assistant_model=None, streamer=None, **kwargs):
@@ -598,5 +636,5 @@ class LookaheadPreTrainedModel(object):
                                  else getattr(self.generation_config, 'eos_token_id', None),
                                  pad_token_id=ga.pad_token_id if ga.pad_token_id is not None else 0,
                                  logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
-                                 stopping_criteria=ga.stopping_criteria)
+                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True))
         return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out
