@@ -4,7 +4,7 @@
  * capture their graphs again after a change.
  *
  * Defaults: everything 0 except key 6 = 12657 (paired wide launches + their fat-wave forms; gate/up and QKV unpaired at <= 4 blocks, QKV over <= 128 regions in two token groups), key 11 = 1 (one step per graph), key 17 = 1
- * (single-launch tree attention), key 24 = 1, key 25 = 13.
+ * (single-launch tree attention), key 24 = 1, key 25 = 13, key 37 = 20 (that attention with SL = 1, DV = 4).
  */
 #ifndef LOOKAHEAD_HIP_LAB_H
 #define LOOKAHEAD_HIP_LAB_H
@@ -60,7 +60,11 @@ extern "C" {
  *         (k_gemm_fatd: four waves = four {gate, up} row-block pairs x all token tiles, only x through LDS; default), 0 = k_gemm_fat
  *         (weights and x through the LDS ring); bit-identical.
  * key 36: the slab launches (o_proj / down) of the multi-block step at 5-8 blocks, 1 = the x fragments of a wave's own token tiles streamed straight
- *         into MFMA operand registers, only the weights through the LDS ring (k_gemm_fat, STG = 2; default), 0 = both through the ring; bit-identical. */
+ *         into MFMA operand registers, only the weights through the LDS ring (k_gemm_fat, STG = 2; default), 0 = both through the ring; bit-identical.
+ * key 37: form of the single-launch tree attention (la_attn1.hip), DV | SL << 4 | ring << 8: DV (2 | 4) workgroups per (head, token block, slice)
+ *         share V's four 32-dim blocks (each streams all of K and 1 / DV of V and stores its own columns of o_proj's operand), SL (1 | 2 | 4) token
+ *         slices, ring (0 | 2 | 3) tiles {K, own V} in flight per wave (0 = K double-buffered, V requested per tile; default 20 = SL 1, DV 4, no ring).  0 = (SL = 2, DV = 1), the
+ *         form every shape takes whose nh * 2 * SL * DV workgroups do not fit one per CU.  Bit-identical results; read at launch / capture. */
 int          la_lab_set(int key, int value);
 int          la_lab_get(int key);          /* current value of a knob (the library default unless la_lab_set changed it) */
 /* key 0: device buffer int64[workgroups][waves][8] the GEMM kernels stamp with wall_clock64() at entry / end of the
