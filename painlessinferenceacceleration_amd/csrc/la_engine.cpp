@@ -204,6 +204,8 @@ static size_t carve(la_llama* m, char* base) {
     m->opart = cv.take<float>((size_t)c.n_heads * m->nsplit * 64 * 128);
     m->mpart = cv.take<float>((size_t)c.n_heads * m->nsplit * 64);
     m->lpart = cv.take<float>((size_t)c.n_heads * m->nsplit * 64);
+    // tests/test_gpu_attn_census.py::_split_partials_tail finds the end of lpart from buffer 1 (state): lpart | cand_val | cand_idx | state
+    // must stay adjacent in this order (it reads lpart to see which attention form a step ran)
     size_t cand = (size_t)(c.vocab / 32) * 4;
     if ((size_t)c.balanced_wg[2] * 8 > cand) cand = (size_t)c.balanced_wg[2] * 8;
     m->cand_val = cv.take<float>(cand * 64);

@@ -1140,6 +1140,11 @@ class LlamaVerifyEngine(object):
         """bf16 [max_blocks * 64][vocab] of the last multi-block step (row = 64 * block + tree row)."""
         return self._view(11, _lib.LA_MB_MAX * 64 * self.shape.vocab * 2, self.dtype).view(_lib.LA_MB_MAX * 64, self.shape.vocab)
 
+    def mhidden(self):
+        """[max_blocks * 64][hidden]: the residual stream of the last multi-block step after the last layer (row = 64 * block + tree
+        row) — the multi-block twin of hidden()."""
+        return self._view(13, _lib.LA_MB_MAX * 64 * self.shape.hidden * 2, self.dtype).view(_lib.LA_MB_MAX * 64, self.shape.hidden)
+
     def mout(self):
         return self._view(12, _lib.LA_MOUT_WORDS * 4, torch.int32)
 

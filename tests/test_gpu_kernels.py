@@ -178,19 +178,32 @@ def test_qkv_post(nh, nkv):
     assert torch.equal(got_k, k_ref)
 
 
-@pytest.mark.parametrize('nh,nkv,nkeys,nsplit,T', [(2, 2, 0, 1, 64), (2, 2, 70, 2, 64), (4, 1, 333, 4, 17), (2, 2, 640, 8, 64),
-                                                   (2, 2, 31, 3, 1), (2, 2, 1500, 8, 64), (2, 2, 1500, 2, 64), (4, 2, 2040, 1, 40),
-                                                   (2, 2, 5, 8, 3)])
+TREE_ATTN_CASES = [(2, 2, 0, 1, 64), (2, 2, 70, 2, 64), (4, 1, 333, 4, 17), (2, 2, 640, 8, 64), (2, 2, 31, 3, 1), (2, 2, 1500, 8, 64),
+                   (2, 2, 1500, 2, 64), (4, 2, 2040, 1, 40), (2, 2, 5, 8, 3), (32, 32, 1400, 8, 64), (32, 8, 1500, 8, 64)]
+
+
+@pytest.mark.parametrize('nh,nkv,nkeys,nsplit,T', TREE_ATTN_CASES)
 @pytest.mark.usefixtures('lab_build')
 def test_tree_attention(nh, nkv, nkeys, nsplit, T):
+    _tree_attention(lib, torch.bfloat16, nh, nkv, nkeys, nsplit, T)
+
+
+@pytest.mark.parametrize('nh,nkv,nkeys,nsplit,T', TREE_ATTN_CASES)
+def test_tree_attention_fp16(nh, nkv, nkeys, nsplit, T):
+    """the same cases and assertions on the float16 lab build"""
+    _tree_attention(_lib.lab_lib_for(torch.float16), torch.float16, nh, nkv, nkeys, nsplit, T)
+
+
+def _tree_attention(lib, dtype, nh, nkv, nkeys, nsplit, T):
     """softmax(QK^T/sqrt(d) + tree mask) V with a mask-free prefix: tolerance 2e-2 relative to max|out|
-    (bf16 P and bf16 output rounding) against an fp32 torch attention over the same bf16 inputs.  Checked form: the single-launch
-    kernel (la_attn1.hip, the default of the single-sequence step; la_debug_set key 17).  The two key-split forms behind it —
+    (16-bit P and output rounding) against an fp32 torch attention over the same 16-bit inputs (bfloat16, and float16 on its
+    build).  Checked form: the single-launch kernel (la_attn1.hip, the default of the single-sequence step; la_debug_set key 17).  The two key-split forms behind it —
     K/V tiles straight into registers, and staged once per workgroup through LDS (key 10) — must agree BITWISE with each other
     (partials and packed output): same arithmetic in the same order, only the way the tiles reach the MFMA operands differs."""
     rs = np.random.RandomState(nkeys + T)
     g = torch.Generator(device=DEV).manual_seed(nkeys)
     max_keys = 2048
+    bf = lambda t: t.to(dtype)
     q = bf(torch.randn(nh, 64, 128, generator=g, device=DEV))
     kmain = bf(torch.randn(nkv, max_keys, 128, generator=g, device=DEV))     # rows >= nkeys are stale garbage
     vmain = bf(torch.randn(nkv, max_keys, 128, generator=g, device=DEV))
@@ -209,7 +222,7 @@ def test_tree_attention(nh, nkv, nkeys, nsplit, T):
     opart = torch.zeros(nh * nsplit * 64 * 128, dtype=torch.float32, device=DEV)
     mpart = torch.zeros(nh * nsplit * 64, dtype=torch.float32, device=DEV)
     lpart = torch.zeros_like(mpart)
-    out = torch.zeros(64 * nh * 128, dtype=torch.bfloat16, device=DEV)
+    out = torch.zeros(64 * nh * 128, dtype=dtype, device=DEV)
     default_form, default_one = lib.la_lab_get(10), lib.la_lab_get(17)
     forms = []
     try:
@@ -245,6 +258,113 @@ def test_tree_attention(nh, nkv, nkeys, nsplit, T):
     err = gu.rel_err(got[:T], ref[:T])
     assert err < 2e-2, err
     assert not torch.isnan(got).any()
+
+
+def _batch_attention_case(rs, n_slots, nh, nkv):
+    """A shuffled row -> slot map with unused (-1) rows, per-slot cursors from {0, 5, 70, 333, 640} and one random tree per slot over
+    its own block rows.  With 3 or more slots, slot 1 owns no row (its workgroups leave at once).
+    -> (seq int32 [64], nkeys int32 [16], rowmask uint64 [64] over BLOCK rows)"""
+    owners = [s for s in range(n_slots) if not (n_slots >= 3 and s == 1)]
+    seq = np.full(64, -1, dtype=np.int32)
+    rows = rs.permutation(64)[:56]                           # 8 rows stay unused
+    for i, r in enumerate(rows):
+        seq[r] = owners[i] if i < len(owners) else owners[rs.randint(len(owners))]      # every owner gets at least one row
+    nkeys = np.zeros(_lib.LA_MAX_SEQ, dtype=np.int32)
+    nkeys[:n_slots] = np.asarray([0, 5, 70, 333, 640])[rs.permutation(5)[np.arange(n_slots) % 5]]
+    rowmask = np.array([1 << t for t in range(64)], dtype=np.uint64)
+    for s in owners:
+        mine = np.nonzero(seq == s)[0]
+        _, local = gu.random_tree(rs, len(mine))
+        for i, r in enumerate(mine):
+            rowmask[r] = sum(1 << int(mine[j]) for j in range(len(mine)) if (int(local[i]) >> j) & 1)
+    return seq, nkeys, rowmask
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize('nh,nkv', [(2, 2), (8, 2), (32, 8)])
+@pytest.mark.parametrize('n_slots,nsplit', [(1, 1), (3, 4), (16, 8), (3, 6), (16, 2)])
+def test_tree_attention_batch(n_slots, nsplit, nh, nkv, dtype):
+    """la_tree_attn_batch (k_tree_attn with grid.z = slot + k_attn_combine) through the C ABI of the product library: per-slot cursors,
+    the row -> slot map and slot_tiles addressing.  Twice on one layout: (a) census inputs — q = 0 and one-hot V, so that row t's output
+    times its key count is the class histogram of the keys it read: exact, max |est - w| < 0.25 (tests/census.py: three 16-bit
+    roundings of a count <= 32 stay under 0.19, one wrong (row, key) pair moves a count by >= 0.5); every key the kernel must not read
+    (other slots' regions, rows past a cursor, other slots' fresh rows) holds a one-hot class too, so a leak counts; (b) Gaussian
+    inputs against an fp64 torch attention over the same 16-bit inputs, the 2e-2 relative bar test_tree_attention states for this
+    arithmetic."""
+    L = _lib.lib_for(dtype)
+    rs = np.random.RandomState(1000 * n_slots + 10 * nsplit + nh)
+    g = torch.Generator(device=DEV).manual_seed(n_slots * 131 + nsplit)
+    slot_keys = 672
+    total = slot_keys * n_slots
+    seq, nkeys, rowmask = _batch_attention_case(rs, n_slots, nh, nkv)
+    bstate = torch.zeros(_lib.LA_BST_WORDS, dtype=torch.int32)
+    bstate[_lib.LA_BST_NKEYS:_lib.LA_BST_NKEYS + _lib.LA_MAX_SEQ] = torch.from_numpy(nkeys)
+    bstate[_lib.LA_BST_SEQ:_lib.LA_BST_SEQ + 64] = torch.from_numpy(seq)
+    bstate = bstate.to(DEV)
+    rm = torch.from_numpy(rowmask.view(np.int64)).to(DEV)
+    rep = nh // nkv
+    live = np.nonzero(seq >= 0)[0]
+    # visibility of every live row over [its slot's region | the 64 fresh rows]
+    vis = torch.zeros(64, total + 64, dtype=torch.bool)
+    for t in live:
+        s0 = int(seq[t]) * slot_keys
+        vis[t, s0:s0 + int(nkeys[seq[t]])] = True
+        vis[t, total:] = torch.tensor([(int(rowmask[t]) >> j) & 1 for j in range(64)], dtype=torch.bool)
+    vis = vis.to(DEV)
+
+    def run(q, kmain, vmain, kfr, vfr):
+        qf = gu.to_packed(q, gu.rf_index(64), 8192).reshape(-1)
+        km = gu.to_packed(kmain, gu.rf_index(total), total * 128).reshape(-1)
+        vm = gu.to_packed(vmain, gu.vf_index(total), total * 128).reshape(-1)
+        kf = gu.to_packed(kfr, gu.rf_index(64), 8192).reshape(-1)
+        vf = gu.to_packed(vfr, gu.vf_index(64), 8192).reshape(-1)
+        opart = torch.zeros(nh * nsplit * 64 * 128, dtype=torch.float32, device=DEV)
+        mpart = torch.zeros(nh * nsplit * 64, dtype=torch.float32, device=DEV)
+        lpart = torch.zeros_like(mpart)
+        out = torch.zeros(64 * nh * 128, dtype=dtype, device=DEV)
+        check(L.la_tree_attn_batch(sp(), ptr(qf), ptr(km), ptr(vm), ptr(kf), ptr(vf), ptr(rm), ptr(bstate), nh, nkv, slot_keys, n_slots,
+                                   nsplit, ptr(opart), ptr(mpart), ptr(lpart), ptr(out)), 'tree_attn_batch')
+        torch.cuda.synchronize()
+        return gu.from_packed(out, gu.xp_index(nh * 128)).double().view(64, nh, 128)
+
+    # (a) census: q = 0, K Gaussian (it must not matter), V one-hot at a random class per key — the same class in every kv head
+    cls_main = torch.from_numpy(rs.randint(0, 128, size=total)).to(DEV)
+    cls_fr = torch.from_numpy(rs.randint(0, 128, size=64)).to(DEV)
+    onehot = lambda c: torch.nn.functional.one_hot(c, 128).to(dtype)[None].expand(nkv, -1, -1).contiguous()
+    got = run(torch.zeros(nh, 64, 128, dtype=dtype, device=DEV), torch.randn(nkv, total, 128, generator=g, device=DEV).to(dtype),
+              onehot(cls_main), torch.randn(nkv, 64, 128, generator=g, device=DEV).to(dtype), onehot(cls_fr))
+    w = torch.zeros(64, 128, dtype=torch.float64, device=DEV)
+    w.index_add_(1, torch.cat([cls_main, cls_fr]), vis.double())
+    assert float(w.max()) <= 32, 'the census bar holds for class counts up to 32'
+    n = w.sum(-1)
+    est = got * (n[:, None, None] / got.sum(-1, keepdim=True).clamp_min(1e-30))
+    dev = (est - w[:, None, :]).abs()[torch.from_numpy(live).to(DEV)]
+    worst = float(dev.max())
+    print(f'[census] la_tree_attn_batch slots {n_slots} splits {nsplit} heads {nh}/{nkv} {dtype}: {len(live) * nh} (row, head) checks, '
+          f'worst deviation {worst:.4f} (bar 0.25)')
+    if not worst < 0.25:
+        i, h, c = np.unravel_index(int(dev.reshape(-1).argmax().cpu()), tuple(dev.shape))
+        t = int(live[i])
+        keys_c = torch.nonzero(torch.cat([cls_main, cls_fr]) == c).reshape(-1).cpu().tolist()
+        raise AssertionError(f'row {t} (slot {seq[t]}, cursor {nkeys[seq[t]]}) head {h} class {c}: read {float(est[t, h, c]):.3f} keys, expected '
+                             f'{int(w[t, c])}; keys of that class (index = slot * {slot_keys} + position, fresh rows from {total}): {keys_c}')
+    assert not torch.isnan(got[torch.from_numpy(live).to(DEV)]).any()
+
+    # (b) Gaussian inputs vs fp64 attention over the same 16-bit inputs
+    q = torch.randn(nh, 64, 128, generator=g, device=DEV).to(dtype)
+    kmain = torch.randn(nkv, total, 128, generator=g, device=DEV).to(dtype)
+    vmain = torch.randn(nkv, total, 128, generator=g, device=DEV).to(dtype)
+    kfr = torch.randn(nkv, 64, 128, generator=g, device=DEV).to(dtype)
+    vfr = torch.randn(nkv, 64, 128, generator=g, device=DEV).to(dtype)
+    got = run(q, kmain, vmain, kfr, vfr)
+    K = torch.cat([kmain, kfr], 1).double().repeat_interleave(rep, 0)             # [nh, total + 64, 128]
+    V = torch.cat([vmain, vfr], 1).double().repeat_interleave(rep, 0)
+    sc = torch.einsum('htd,hkd->htk', q.double(), K) / math.sqrt(128)
+    sc = sc.masked_fill(~vis[None], float('-inf'))
+    li = torch.from_numpy(live).to(DEV)
+    ref = torch.einsum('htk,hkd->thd', torch.softmax(sc[:, li], -1), V)
+    err = gu.rel_err(got[li], ref)
+    assert err < 2e-2, err
 
 
 def test_accept_scan_matches_reference_vectors():
