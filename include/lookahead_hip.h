@@ -43,7 +43,7 @@ extern "C" {
 #define LA_MOE_MAX_E      8   /* experts per mixture-of-experts layer (Mixtral: 8, top-2) */
 
 /* ABI version: bumped when a signature changes. */
-#define LA_ABI_VERSION  15   /* bumped whenever a struct layout or an entry point changes */
+#define LA_ABI_VERSION  16   /* bumped whenever a struct layout or an entry point changes */
 int          la_abi_version(void);   /* == LA_ABI_VERSION of the header the library was built from */
 /* Storage / MFMA-input type of the loaded library: 0 = bfloat16 (liblookahead_hip.so), 1 = float16 (liblookahead_hip_f16.so, the
  * dtype the reference's examples and benchmarks run, lookahead/benchmarks/llama_benchmark.py:27).  The two libraries are the same
@@ -537,6 +537,44 @@ int la_llama_penalty_launches(la_llama* m);
 int la_penalty_argmax(void* stream, const void* d_logits, int vocab, int n_rows, const uint32_t* d_bitmap, const int32_t* d_ids,
                       const uint64_t* d_rowmask, const float* d_penalty, int32_t* d_argmax);
 int la_penalty_transform(void* stream, const void* d_x, int n, const float* d_penalty, void* d_out);
+
+/* ---- sampling on the device -----------------------------------------------------------------------------------------------------
+ * do_sample as a stage of the verify step: between lm_head and the accept walk one workgroup per live tree row picks the row's
+ * SAMPLED token (temperature -> top-k -> top-p -> draw, transformers' order) and writes it where the argmax went; the accept walk,
+ * the commit and the result blocks are unchanged, so every step form (la_llama_step graph / eager, la_lookahead_decode,
+ * la_llama_bstep, la_llama_mstep mode 0 and 1; not wide trees: LA_E_ARG) keeps its contract.  The draw is a pure function of
+ * (seed, stream, position, token), never of call order: a draft child is accepted iff it equals the token sampled at its parent
+ * (ancestral sampling, exactly), and the same seed gives the same sequence with and without drafts, whatever the trees were.
+ * The sampler of one row (x = the 16-bit logits; thresholds are 16-bit keys: storage bits in value order, -0 == +0, NaN never kept):
+ *   1. repetition penalty, when la_llama_set_repetition_penalty is on too: exactly la_penalty_argmax's rewrite of the context members
+ *   2. z_v = x_v / temperature in fp32
+ *   3. top-k: keep v iff x_v >= the k-th largest value (ties at the threshold stay; top_k <= 0 or >= vocab: off) - exact radix select
+ *   4. top-p over the survivors: q_v = floor(expf(z_v - z_max) * 2^32) summed as 64-bit integers (order-independent, the same bits
+ *      on every run and step path); keep v iff the mass of survivors with a value strictly greater than x_v is < top_p * Z
+ *      (TopPLogitsWarper, min_tokens_to_keep = 1, except that ALL tokens tied with the lowest kept value stay); top_p >= 1: off
+ *   5. Gumbel-max draw over the kept set: argmax_v (z_v + g_v), lowest index among equals; g_v = -logf(-logf(u_v)),
+ *      u_v = (k_v + 0.5) * 2^-23, k_v = the top 23 bits of token v's Philox word; Philox4x32-10 with key (seed lo, seed hi) and
+ *      counter (v >> 2, position, stream, 0), word v & 3; position = pos[row] + 1 = the index in the unpadded sequence of the
+ *      token being chosen (the prompt's last row chooses the token at index len(prompt))
+ * This is a sampler of its own: the same distribution as softmax + multinomial over the warped logits (up to the tie rule of 4), not
+ * torch.multinomial's tokens - the random numbers differ.
+ *   la_llama_set_sampling      per model; enabled = 0 is the default (a step then launches exactly what it launched before the stage
+ *                              existed).  Synchronises `stream`; switching the stage on or off drops the model's captured graphs, new
+ *                              values only rewrite the device words the stage reads.  temperature > 0.
+ *   la_llama_sampling_stream   the stream word of `slot` (default: the slot index) - what tells two sequences of one seed apart
+ *   la_llama_sample_launches   steps launched with the stage since la_llama_create
+ *   la_sample_rows             the row stage alone: logits [n_rows <= 64][vocab] of the library's 16-bit type, d_pos[n_rows] (the
+ *                              draw uses d_pos[r] + 1); d_bitmap / d_penalty both null = no penalty, else as la_penalty_argmax;
+ *                              -> d_tok[n_rows], d_info[n_rows][4] = {top-k threshold key (0 = off), top-p threshold key (0 = off),
+ *                              kept count, 0} (d_info may be null)
+ *   la_sample_bits             d_out[v] = the Philox word of token v at (seed, stream_id, position) */
+int la_llama_set_sampling(la_llama* m, void* stream, int enabled, uint64_t seed, float temperature, int top_k, float top_p);
+int la_llama_sampling_stream(la_llama* m, void* stream, int slot, uint32_t stream_id);
+int la_llama_sample_launches(la_llama* m);
+int la_sample_rows(void* stream, const void* d_logits, int vocab, int n_rows, const int32_t* d_pos, uint32_t stream_id, uint64_t seed,
+                   float temperature, int top_k, float top_p, const uint32_t* d_bitmap, const int32_t* d_ids, const uint64_t* d_rowmask,
+                   const float* d_penalty, int32_t* d_tok, int32_t* d_info);
+int la_sample_bits(void* stream, uint64_t seed, uint32_t stream_id, uint32_t position, int vocab, uint32_t* d_out);
 
 /* ---- native decode loop: the per-step host work of lookahead_generation (pretrained_model.py:1172-1240) without the
  * interpreter: hier_get(last max_query_length tokens) -> la_llama_step -> stream_put, until max_length / eos / max_steps.

@@ -355,4 +355,24 @@ int la_trie_hier_get_wg(void* stream, const la_trie_query* q) {
     WRAP(lk_trie_hier_get_wg((hipStream_t)stream, a, q->B));
 }
 
+// ---- sampling on the device (la_sample.hip): the row stage / the Philox words alone (unit parity)
+int la_sample_rows(void* stream, const void* d_logits, int vocab, int n_rows, const int32_t* d_pos, uint32_t stream_id, uint64_t seed,
+                   float temperature, int top_k, float top_p, const uint32_t* d_bitmap, const int32_t* d_ids, const uint64_t* d_rowmask,
+                   const float* d_penalty, int32_t* d_tok, int32_t* d_info) {
+    const int pen = d_bitmap != nullptr;
+    if (!d_logits || !d_pos || !d_ids || !d_rowmask || !d_tok || (pen && !d_penalty) || n_rows < 1 || n_rows > LA_TREE_MAX || vocab <= 0 ||
+        (vocab & 31) || lk_sample_lds_bytes(vocab, pen) > 64 * 1024 || !(temperature > 0.f)) return LA_E_ARG;
+    SampArgs sa{};
+    sa.p.kind = LA_PEN_ROWS; sa.p.vocab = vocab; sa.p.n_slots = 1; sa.p.nblk = 1; sa.p.n_rows = n_rows;
+    sa.p.logits = d_logits; sa.p.bitmaps = (unsigned*)d_bitmap; sa.p.penalty = d_penalty; sa.p.ids = d_ids;
+    sa.p.rowmask = (const unsigned long long*)d_rowmask; sa.p.out = d_tok;
+    sa.pen = pen; sa.pos = d_pos; sa.params = nullptr; sa.seed_lo = (unsigned)seed; sa.seed_hi = (unsigned)(seed >> 32);
+    sa.stream_id = stream_id; sa.temperature = temperature; sa.top_p = top_p; sa.top_k = top_k; sa.info = d_info;
+    WRAP(lk_sample_rows((hipStream_t)stream, sa));
+}
+int la_sample_bits(void* stream, uint64_t seed, uint32_t stream_id, uint32_t position, int vocab, uint32_t* d_out) {
+    if (!d_out || vocab <= 0) return LA_E_ARG;
+    WRAP(lk_sample_bits((hipStream_t)stream, (unsigned)seed, (unsigned)(seed >> 32), stream_id, position, vocab, d_out));
+}
+
 }  // extern "C"

@@ -90,6 +90,12 @@ struct la_llama {
     float penalty = 1.0f;
     bool pen_on = false;
     int pen_launches = 0;
+    // sampling on the device (la_sample.hip): the parameter block (LA_SAMP_* words: seed, temperature, top_k, top_p, one stream word
+    // per slot) the captured graphs read — a new value rewrites device words only, switching the stage on / off drops the graphs
+    unsigned* samp_par = nullptr;
+    unsigned samp_stream[LA_SAMP_WORDS - LA_SAMP_STREAM];      // host mirror of the stream words (default: the slot index)
+    bool samp_on = false;
+    int samp_launches = 0;
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -262,6 +268,7 @@ static size_t carve(la_llama* m, char* base) {
     }
     m->pen_bits = cv.take<unsigned>((size_t)m->n_slots * (c.vocab / 32));
     m->pen_val = cv.take<float>(64);
+    m->samp_par = cv.take<unsigned>(LA_SAMP_WORDS);
     return align_up(cv.off, 256);
 }
 
@@ -360,6 +367,7 @@ extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_
     size_t need = carve(m, (char*)ws);
     if ((int64_t)need > ws_bytes) { la_set_error("workspace too small"); delete m; return nullptr; }
     m->ws = (char*)ws;
+    for (int i = 0; i < LA_SAMP_WORDS - LA_SAMP_STREAM; ++i) m->samp_stream[i] = (unsigned)i;
     m->graph_ready = m->bgraph_ready = false;
     m->graph_exec = m->bgraph_exec = nullptr;
     m->graph_stream = nullptr;
@@ -671,10 +679,21 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
         pa.logits = m->logits; pa.bitmaps = m->pen_bits; pa.penalty = m->pen_val; pa.ids = m->ids;
         pa.rowmask = (const unsigned long long*)m->rowmask; pa.state = batch ? m->bstate : m->state; pa.in = m->bin; pa.out = am_rows;
     }
+    // sampling (la_sample.hip): the sampled token of every live row takes the place of the candidate reduction AND of k_pen_argmax
+    // (the stage applies the penalty itself); the walk kernels and k_pen_update run as they are
+    const bool samp = m->samp_on;
+    SampArgs sa{};
+    if (samp) {
+        sa.p.kind = batch ? LA_PEN_BATCH : LA_PEN_SINGLE; sa.p.vocab = c.vocab; sa.p.n_slots = m->n_slots; sa.p.nblk = 1;
+        sa.p.logits = m->logits; sa.p.bitmaps = m->pen_bits; sa.p.penalty = m->pen_val; sa.p.ids = m->ids;
+        sa.p.rowmask = (const unsigned long long*)m->rowmask; sa.p.state = batch ? m->bstate : m->state; sa.p.in = m->bin; sa.p.out = am_rows;
+        sa.pen = pen ? 1 : 0; sa.pos = m->pos; sa.params = m->samp_par;
+    }
+    const bool rows_stage = pen || samp;         // a row stage writes the ARGMAX words
     if (c.balanced_wg[2] > 0) {
         KCHK(lk_gemm64r_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, c.balanced_wg[2], m->logits, m->cand_val, m->cand_idx));
         P(KC_OTHER);
-        if (!pen && !batch && !g_la_split_head_tail) {
+        if (!rows_stage && !batch && !g_la_split_head_tail) {
             // argmax finalize + accept walk + result hand-over in ONE launch, the KV commit after it: the host reads the accepted
             // tokens (and starts its trie update / next query) while the commit kernel still runs
             KCHK(lk_step_tail(st, m->cand_val, m->cand_idx, c.balanced_wg[2], m->ids, m->rowmask, m->state, (int*)zc_out));
@@ -682,13 +701,14 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
             P(KC_N);
             return join_pf();
         }
-        if (!pen) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, c.balanced_wg[2], am_rows));
+        if (!rows_stage) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, c.balanced_wg[2], am_rows));
     } else {
         KCHK(lk_gemm64_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, m->lm_rb, m->logits, m->cand_val, m->cand_idx));
         P(KC_OTHER);
-        if (!pen) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, lk_logits_cand_slots(c.vocab, m->lm_rb), am_rows));
+        if (!rows_stage) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, lk_logits_cand_slots(c.vocab, m->lm_rb), am_rows));
     }
-    if (pen) KCHK(lk_pen_argmax(st, pa));
+    if (samp) KCHK(lk_sample_rows(st, sa));
+    else if (pen) KCHK(lk_pen_argmax(st, pa));
     if (batch) {
         KCHK(lk_accept_scan_b(st, m->bin, m->ids, m->rowmask, m->bstate, m->n_slots, c.max_keys, ring));
         if (pen) KCHK(lk_pen_update(st, pa));
@@ -749,6 +769,7 @@ static int bstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     const int target = m->nsplit / active > 1 ? m->nsplit / active : 1;
     while (v < 3 && bsplit > target && bsplit % 2 == 0) { bsplit /= 2; ++v; }
     if (m->pen_on) ++m->pen_launches;
+    if (m->samp_on) ++m->samp_launches;
     if (eager) {
         int rc = enqueue_step(m, st, nullptr, true, nullptr, nullptr, bsplit);
         if (rc != LA_OK) return rc;
@@ -788,6 +809,7 @@ static int mb_split(int nblk, int n_heads = 32, int cus = 256) {
 static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = false) {
     const la_llama_config& c = m->cfg;
     if (!m->qkv_fused) { la_set_error("mstep needs the fused QKV image (gemm_cfg[1] >= 0)"); return LA_E_ARG; }
+    if (m->samp_on && wide) { la_set_error("mstep: device sampling has no wide-tree form (la_llama_set_sampling(enabled = 0) + host walk)"); return LA_E_ARG; }
     if (m->pen_on && wide) { la_set_error("mstep: the device repetition penalty has no wide-tree form (la_llama_set_repetition_penalty(1.0) + host walk)"); return LA_E_ARG; }
     const int M = nblk * 64;
     const int npass_rows = (nblk <= 2 ? nblk : ((nblk + 3) / 4) * 4) * 64;     // rows whole passes write (slab stride)
@@ -891,6 +913,15 @@ static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = fals
         pa.kind = LA_PEN_MBLOCK; pa.vocab = c.vocab; pa.n_slots = m->n_slots; pa.nblk = nblk;
         pa.logits = m->mb_logits; pa.bitmaps = m->pen_bits; pa.penalty = m->pen_val; pa.ids = m->mb_ids;
         pa.rowmask = (const unsigned long long*)m->mb_rowmask; pa.state = m->mb_out; pa.meta = m->mb_meta; pa.out = m->mb_out + LA_MOUT_ARGMAX;
+    }
+    if (m->samp_on) {
+        SampArgs sa{};
+        sa.p = pa;
+        sa.p.kind = LA_PEN_MBLOCK; sa.p.vocab = c.vocab; sa.p.n_slots = m->n_slots; sa.p.nblk = nblk; sa.p.logits = m->mb_logits;
+        sa.p.rowmask = (const unsigned long long*)m->mb_rowmask; sa.p.ids = m->mb_ids; sa.p.meta = m->mb_meta; sa.p.out = m->mb_out + LA_MOUT_ARGMAX;
+        sa.pen = m->pen_on ? 1 : 0; sa.pos = m->mb_pos; sa.params = m->samp_par;
+        KCHK(lk_sample_rows(st, sa));
+    } else if (m->pen_on) {
         KCHK(lk_pen_argmax(st, pa));
     } else
     KCHK(lk_mb_argmax(st, m->mb_cand_val, m->mb_cand_idx, lk_mb_cand_slots(lwg), nblk, m->mb_out + LA_MOUT_ARGMAX));
@@ -910,6 +941,7 @@ static int mstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(m->mb_in, host_in, LA_MIN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
     if (m->pen_on) ++m->pen_launches;
+    if (m->samp_on) ++m->samp_launches;
     if (eager) {
         int rc = enqueue_mstep(m, st, nblk, wide);
         if (rc != LA_OK) return rc;
@@ -944,6 +976,7 @@ extern "C" int la_llama_mstep_trie(la_llama* m, void* stream, int nblk, const in
     hipStream_t st = (hipStream_t)stream;
     KCHK(lk_mb_fill_from_trie(st, d_ids, d_rowmask, d_n, slots, limits, last_tok, nblk, m->mb_in));
     if (m->pen_on) ++m->pen_launches;
+    if (m->samp_on) ++m->samp_launches;
     const int gi = nblk;
     if (m->mready[gi] && m->mepoch[gi] != g_la_graph_epoch) {
         (void)hipGraphExecDestroy(m->mgraphs[gi]);
@@ -1015,6 +1048,7 @@ extern "C" int la_llama_step(la_llama* m, void* stream, const int32_t* host_in, 
     }
     m->seq_expected += 1;
     if (m->pen_on) ++m->pen_launches;
+    if (m->samp_on) ++m->samp_launches;
     HIPCHK(hipGraphLaunch(long_ctx ? m->graph_long : m->graph_exec, st));
     return LA_OK;
 }
@@ -1042,6 +1076,7 @@ extern "C" int la_llama_step_eager(la_llama* m, void* stream, const int32_t* hos
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(m->in, host_in, LA_IN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
     if (m->pen_on) ++m->pen_launches;
+    if (m->samp_on) ++m->samp_launches;
     int rc = enqueue_step(m, st, nullptr, false, nullptr, nullptr, 0, host_in[LA_IN_NKEYS_HINT] + LA_TREE_MAX > m->attn_thr);
     if (rc != LA_OK) return rc;
     if (host_out)
@@ -1254,6 +1289,39 @@ extern "C" int la_llama_set_repetition_penalty(la_llama* m, void* stream, float 
     m->pen_on = on;
     return LA_OK;
 }
+
+// ---- sampling on the device (la_sample.hip) ----------------------------------------------------------------------------
+extern "C" int la_llama_set_sampling(la_llama* m, void* stream, int enabled, uint64_t seed, float temperature, int top_k, float top_p) {
+    if (!m) return LA_E_ARG;
+    const bool on = enabled != 0;
+    if (on && (!(temperature > 0.f) || !(temperature <= 3.0e38f) || top_p != top_p)) { la_set_error("sampling: temperature must be a finite float > 0 and top_p a number"); return LA_E_ARG; }
+    if (on && ((m->cfg.vocab & 31) || lk_sample_lds_bytes(m->cfg.vocab, 1) > 64 * 1024)) { la_set_error("sampling: the row stage does not fit this vocabulary"); return LA_E_RANGE; }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(st));                       // no step in flight reads the block / runs a graph that is dropped below
+    if (on) {
+        unsigned w[LA_SAMP_WORDS] = {(unsigned)seed, (unsigned)(seed >> 32), 0u, (unsigned)top_k, 0u};
+        memcpy(&w[LA_SAMP_TEMP], &temperature, 4);
+        memcpy(&w[LA_SAMP_TOPP], &top_p, 4);
+        memcpy(&w[LA_SAMP_STREAM], m->samp_stream, sizeof(m->samp_stream));
+        HIPCHK(hipMemcpyAsync(m->samp_par, w, sizeof(w), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));                   // w lives on this stack frame
+    }
+    if (on != m->samp_on) drop_graphs(m);
+    m->samp_on = on;
+    return LA_OK;
+}
+
+extern "C" int la_llama_sampling_stream(la_llama* m, void* stream, int slot, uint32_t stream_id) {
+    if (!m || slot < 0 || slot >= m->n_slots || slot >= LA_SAMP_WORDS - LA_SAMP_STREAM) return LA_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    m->samp_stream[slot] = stream_id;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(m->samp_par + LA_SAMP_STREAM + slot, &m->samp_stream[slot], sizeof(unsigned), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return LA_OK;
+}
+
+extern "C" int la_llama_sample_launches(la_llama* m) { return m ? m->samp_launches : LA_E_ARG; }
 
 extern "C" int la_llama_penalty_seed(la_llama* m, void* stream, int slot, const int32_t* tokens, int n) {
     if (!m || slot < 0 || slot >= m->n_slots || n < 0 || (n > 0 && !tokens)) return LA_E_ARG;

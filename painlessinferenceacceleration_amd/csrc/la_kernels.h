@@ -173,3 +173,21 @@ size_t lk_pen_lds_bytes(int vocab);
 int lk_pen_argmax(hipStream_t st, const PenArgs& a);
 int lk_pen_update(hipStream_t st, const PenArgs& a);
 int lk_pen_transform(hipStream_t st, const void* x, int n, const float* d_penalty, void* out);
+
+// ---- sampling on the device (la_sample.hip): the seeded temperature / top-k / top-p token of every live tree row, written to the
+// ARGMAX word of the row in place of the candidate reduction (and of k_pen_argmax: the stage applies the penalty itself)
+enum { LA_SAMP_SEED_LO = 0, LA_SAMP_SEED_HI = 1, LA_SAMP_TEMP = 2, LA_SAMP_TOPK = 3, LA_SAMP_TOPP = 4, LA_SAMP_STREAM = 8,
+       LA_SAMP_WORDS = 8 + 64 };     // the device parameter block (32-bit words; one stream word per slot from LA_SAMP_STREAM on)
+struct SampArgs {
+    PenArgs p;                        // row addressing (kind, state, in, meta), logits, out; bitmaps / penalty / ids / rowmask when `pen`
+    int pen;                          // 1: apply the repetition penalty to the context members first (p.bitmaps, p.penalty)
+    const int* pos;                   // RoPE position of every row (same index as the logits row)
+    const unsigned* params;           // device parameter block (LA_SAMP_*), or null: the values below (unit entry)
+    unsigned seed_lo, seed_hi, stream_id;
+    float temperature, top_p;
+    int top_k;
+    int* info;                        // nullable: [rows][4] = {top-k threshold key, top-p threshold key, kept count, 0}
+};
+size_t lk_sample_lds_bytes(int vocab, int pen);
+int lk_sample_rows(hipStream_t st, const SampArgs& a);
+int lk_sample_bits(hipStream_t st, unsigned seed_lo, unsigned seed_hi, unsigned stream_id, unsigned position, int vocab, unsigned* out);

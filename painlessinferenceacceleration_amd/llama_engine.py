@@ -699,6 +699,7 @@ class LlamaVerifyEngine(object):
         self.n_keys = 0
         self.repetition_penalty = 1.0
         self._pen_ctx = {}
+        self.sampling = False
         self.reset()
 
     def __del__(self):
@@ -752,6 +753,25 @@ class LlamaVerifyEngine(object):
     def penalty_launches(self):
         """steps launched with the penalty stage since the engine was created"""
         return int(self._lib.la_llama_penalty_launches(self._h))
+
+    # ---- sampling on the device (csrc/la_sample.hip) ------------------------------------------------------------------------
+    def set_sampling(self, enabled, seed=0, temperature=1.0, top_k=0, top_p=1.0):
+        """do_sample as a stage of every verify step (step / decode_native / bstep / mstep, first token after a prefill included):
+        the seeded temperature / top-k / top-p token of every live tree row is drawn on the device where the argmax went, and the
+        fused accept walk runs on it.  The draw depends on (seed, stream of the slot, position, token) only, so the same seed gives
+        the same sequence with and without drafts.  Off (the default): the steps launch exactly what they launch without the
+        stage.  With set_repetition_penalty on as well, the stage penalises the context members first.  top_k 0 / top_p 1.0: off."""
+        check(self._lib.la_llama_set_sampling(self._h, self._sp(), 1 if enabled else 0, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              float(temperature), int(top_k), float(top_p)), 'set_sampling')
+        self.sampling = bool(enabled)
+
+    def sampling_stream(self, slot, stream_id):
+        """the stream word of `slot` (default: the slot index): what tells the sequences of one seed apart"""
+        check(self._lib.la_llama_sampling_stream(self._h, self._sp(), int(slot), int(stream_id) & 0xFFFFFFFF), 'sampling_stream')
+
+    def sample_launches(self):
+        """steps launched with the sampling stage since the engine was created"""
+        return int(self._lib.la_llama_sample_launches(self._h))
 
     def penalty_context(self, slot=0):
         """uint32 [vocab / 32]: the context bitmap of `slot` (bit t of word t // 32 <=> token t is in the set)"""

@@ -70,6 +70,56 @@ def device_repetition_penalty(logits_processor, engine, do_sample=False, enabled
     return penalty
 
 
+def device_sampling(logits_processor, engine, do_sample=False, seed=None, enabled=True):
+    """The parameter set {'seed', 'temperature', 'top_k', 'top_p', 'penalty'} when a do_sample request can run as the engine's device
+    stage (LlamaVerifyEngine.set_sampling: csrc/la_sample.hip), else None (-> the host walk, exactly as without this stage).  All of:
+    `do_sample`; `seed` (decoding_kwargs['sample_seed']) an int — the stage is opt-in through that key; `enabled`
+    (decoding_kwargs['device_processors'], default True); an engine that has the stage; and a list that is exactly
+        [RepetitionPenaltyLogitsProcessor?] + [TemperatureLogitsWarper?, TopKLogitsWarper?, TopPLogitsWarper?]
+    in that order, each the exact transformers type (a subclass may override __call__) with filter_value == -inf,
+    min_tokens_to_keep == 1 and temperature > 0.  'penalty' is None without the processor; top_k 0 / top_p 1.0 mean off."""
+    if not enabled or not do_sample or isinstance(seed, bool) or not isinstance(seed, int):
+        return None
+    if not hasattr(engine, 'set_sampling'):
+        return None
+    from transformers import RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper
+    items = list(logits_processor) if logits_processor is not None else []
+    out = {'seed': int(seed) & 0xFFFFFFFFFFFFFFFF, 'temperature': 1.0, 'top_k': 0, 'top_p': 1.0, 'penalty': None}
+    if items and type(items[0]) is RepetitionPenaltyLogitsProcessor:
+        penalty = device_repetition_penalty(items[:1], engine, do_sample=False, enabled=True)
+        if penalty is None:
+            return None
+        out['penalty'] = penalty
+        items = items[1:]
+    order = (TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper)
+    at = 0
+    for proc in items:
+        while at < 3 and type(proc) is not order[at]:
+            at += 1
+        if at == 3:                                  # not a warper of the three, out of order, or one type twice
+            return None
+        if at == 0:
+            t = getattr(proc, 'temperature', None)
+            if isinstance(t, bool) or not isinstance(t, (int, float)) or not t > 0:
+                return None
+            out['temperature'] = float(t)
+        else:
+            if getattr(proc, 'filter_value', None) != -float('inf') or getattr(proc, 'min_tokens_to_keep', 1) != 1:
+                return None
+            if at == 1:
+                k = getattr(proc, 'top_k', None)
+                if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+                    return None
+                out['top_k'] = int(k)
+            else:
+                p = getattr(proc, 'top_p', None)
+                if not isinstance(p, float) or not 0.0 <= p <= 1.0:
+                    return None
+                out['top_p'] = float(p)
+        at += 1
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- generate() front door
 _GEN_FIELDS = ('max_length', 'max_new_tokens', 'min_length', 'min_new_tokens', 'eos_token_id', 'pad_token_id', 'do_sample',
                'repetition_penalty', 'no_repeat_ngram_size', 'bad_words_ids', 'temperature', 'top_k', 'top_p', 'max_time',

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from .lookahead_cache import LookaheadCache
 from .lookahead_generation_utils import (GenerationMode, LookaheadDecoderOnlyOutput, device_repetition_penalty,
-                                          resolve_generate_args)
+                                          device_sampling, resolve_generate_args)
 
 _ONE = np.array([1], dtype=np.uint64)
 
@@ -275,7 +275,16 @@ class LookaheadPreTrainedModel(object):
         if sequential and scores is None and not wide and gather is None and not decoding_kwargs.get('device_trie', False):
             dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample,
                                                     enabled=decoding_kwargs.get('device_processors', True))
-        if dev_penalty is not None:
+        # a do_sample request that names decoding_kwargs['sample_seed'] and whose list is [repetition penalty?] + [temperature?,
+        # top-k?, top-p?] runs as the sampling stage of the device step (csrc/la_sample.hip: the seeded draw of every tree row,
+        # then the same accept walk) under the same conditions; without the key it takes the host walk exactly as before
+        dev_sample = None
+        if sequential and scores is None and not wide and gather is None and not decoding_kwargs.get('device_trie', False):
+            dev_sample = device_sampling(logits_processor, eng, do_sample=do_sample, seed=decoding_kwargs.get('sample_seed', None),
+                                         enabled=decoding_kwargs.get('device_processors', True))
+        if dev_sample is not None:
+            dev_penalty = dev_sample['penalty']
+        if dev_penalty is not None or dev_sample is not None:
             sequential = False
         native_loop = (not sequential and streamer is None and dm.split('_')[0] == 'hier' and not wide
                        and custom_stop is None and gather is None and scores is None
@@ -303,6 +312,9 @@ class LookaheadPreTrainedModel(object):
         try:
             if dev_penalty is not None:
                 eng.set_repetition_penalty(dev_penalty)      # prefill seeds the context set with the prompt
+            if dev_sample is not None:
+                eng.sampling_stream(0, 0)
+                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
             while True:
                 if first:
                     host_row = sequential or scores is not None      # the last prompt row's logits must stay readable
@@ -414,6 +426,8 @@ class LookaheadPreTrainedModel(object):
         finally:
             if dev_penalty is not None:
                 eng.set_repetition_penalty(1.0)              # also after an exception: the next request starts without the stage
+            if dev_sample is not None:
+                eng.set_sampling(False)
             # an exception mid-generation must not leave this request's stream buffer / input frequencies behind (they would
             # mix into the next request); the reference flushes on the normal path only (pretrained_model.py:1236-1239)
             if not flushed:
@@ -438,18 +452,23 @@ class LookaheadPreTrainedModel(object):
     # ---------------------------------------------------------------------------------- plain greedy (mode off)
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, eos_token_id=None, logits_processor=None, do_sample=False,
-                      stopping_criteria=None, device_processors=True):
+                      stopping_criteria=None, device_processors=True, sample_seed=None):
         """Plain decoding through the same engine (T=1 blocks): the `use_lookahead=False` leg of the reference's
         examples (examples/llama_example.py:39-69).  With a processor list or sampling each token is picked on the host
-        from the block's logits row (forward-only step + commit) — except a list that is exactly one repetition penalty, which
-        runs as the device stage lookahead_generation uses (device_processors=False: the host pick)."""
+        from the block's logits row (forward-only step + commit) — except a list that is exactly one repetition penalty, or a
+        do_sample request with an int `sample_seed` whose list device_sampling accepts, which run as the device stages
+        lookahead_generation uses (device_processors=False: the host pick).  With the same seed this is the no-draft comparator of
+        the sampling lookahead loop: token for token the same sequence."""
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         seq = input_ids[0].tolist()
         eng = self.engine
         eng.reset()
         host_pick = do_sample or (logits_processor is not None and len(logits_processor) > 0)
         dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample, enabled=device_processors) if host_pick else None
-        if dev_penalty is not None:
+        dev_sample = device_sampling(logits_processor, eng, do_sample=do_sample, seed=sample_seed, enabled=device_processors) if host_pick else None
+        if dev_sample is not None:
+            dev_penalty = dev_sample['penalty']
+        if dev_penalty is not None or dev_sample is not None:
             host_pick = False
         custom_stop = _custom_stop(stopping_criteria)        # the caller's criteria besides the length bound, once per token
 
@@ -465,6 +484,9 @@ class LookaheadPreTrainedModel(object):
         try:
             if dev_penalty is not None:
                 eng.set_repetition_penalty(dev_penalty)
+            if dev_sample is not None:
+                eng.sampling_stream(0, 0)
+                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
             tok = eng.prefill(seq, fast=False) if host_pick else eng.prefill(seq)
             if host_pick:
                 tok = pick((len(seq) - 1) % 64)
@@ -481,6 +503,8 @@ class LookaheadPreTrainedModel(object):
         finally:
             if dev_penalty is not None:
                 eng.set_repetition_penalty(1.0)
+            if dev_sample is not None:
+                eng.set_sampling(False)
         return torch.tensor([seq], dtype=torch.long, device=input_ids.device)
 
     # ------------------------------------------------------------------------------------------- front door
@@ -518,7 +542,11 @@ class LookaheadPreTrainedModel(object):
         if self._get_generation_mode(dk) == GenerationMode.LOOKAHEAD_GENERATION:
             dk['generation_mode'] = GenerationMode.LOOKAHEAD_GENERATION
             dk['do_sample'] = ga.do_sample
-            return self.lookahead_generation(input_ids, logits_processor=ga.logits_processor if len(ga.logits_processor) else None,
+            la_procs = ga.logits_processor
+            if ga.do_sample and 'sample_seed' in dk:         # opt-in: the config-derived warpers reach the lookahead branch too
+                from transformers import LogitsProcessorList
+                la_procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
+            return self.lookahead_generation(input_ids, logits_processor=la_procs if len(la_procs) else None,
                                              stopping_criteria=ga.stopping_criteria, pad_token_id=ga.pad_token_id,
                                              eos_token_id=ga.eos_token_id, output_scores=ga.output_scores or None,
                                              return_dict_in_generate=ga.return_dict_in_generate,
@@ -528,7 +556,8 @@ class LookaheadPreTrainedModel(object):
         out = self.greedy_search(input_ids, ga.max_length, ga.eos_token_id if ga.eos_token_id is not None
                                  else getattr(self.generation_config, 'eos_token_id', None),
                                  logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
-                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True))
+                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True),
+                                 sample_seed=dk.get('sample_seed', None))
         return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out
 
     def stream_generate(self, *args, **kwargs):

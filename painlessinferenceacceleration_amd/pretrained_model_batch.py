@@ -22,7 +22,8 @@ import torch
 
 from . import _lib
 from .lookahead_cache import LookaheadCache
-from .lookahead_generation_utils import LookaheadDecoderOnlyOutput, device_repetition_penalty, resolve_generate_args
+from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, device_repetition_penalty, device_sampling,
+                                          resolve_generate_args)
 from .pretrained_model import _custom_stop, _max_length_of
 
 _ONE = np.array([1], dtype=np.uint64)
@@ -226,9 +227,19 @@ class LookaheadPreTrainedModel(object):
                 min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX:
             dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=bool(decoding_kwargs.get('do_sample', False)),
                                                     enabled=decoding_kwargs.get('device_processors', True))
-        if dev_penalty is not None:
+        # a do_sample request with decoding_kwargs['sample_seed'] and a list device_sampling accepts: the sampling stage of the
+        # device step (csrc/la_sample.hip) under the same conditions, stream word of a slot = its batch index
+        dev_sample = None
+        if sequential and scores is None and gather is None and not decoding_kwargs.get('device_trie', False) and \
+                min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX:
+            dev_sample = device_sampling(logits_processor, eng, do_sample=bool(decoding_kwargs.get('do_sample', False)),
+                                         seed=decoding_kwargs.get('sample_seed', None),
+                                         enabled=decoding_kwargs.get('device_processors', True))
+        if dev_sample is not None:
+            dev_penalty = dev_sample['penalty']
+        if dev_penalty is not None or dev_sample is not None:
             sequential = False
-            decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the penalty stage)
+            decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the penalty / sampling stage)
         finished_rows = [None] * bs
         batch_indices = list(range(bs))
         eos_set = set(eos_token_id) if eos_token_id is not None else set()
@@ -239,6 +250,10 @@ class LookaheadPreTrainedModel(object):
                 eng.set_repetition_penalty(dev_penalty)
                 for i in range(bs):
                     eng.seed_penalty_context(i, ids0[i].tolist())
+            if dev_sample is not None:
+                for i in range(bs):
+                    eng.sampling_stream(i, i)
+                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
             # prefill: valid prompt tokens of every sample, packed into shared 64-row chain blocks
             prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
             multi = bool(getattr(eng, 'max_blocks', 0))
@@ -481,6 +496,8 @@ class LookaheadPreTrainedModel(object):
         finally:
             if dev_penalty is not None:
                 eng.set_repetition_penalty(1.0)          # also after an exception: the next request starts without the stage
+            if dev_sample is not None:
+                eng.set_sampling(False)
         if streamer is not None:
             streamer.end()
         seqs = np.full((bs, max_cur + 1), pad, dtype=np.int64)
@@ -528,7 +545,8 @@ class LookaheadPreTrainedModel(object):
 
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, attention_mask=None, eos_token_id=None, pad_token_id=0,
-                      logits_processor=None, do_sample=False, stopping_criteria=None, device_processors=True):
+                      logits_processor=None, do_sample=False, stopping_criteria=None, device_processors=True,
+                      sample_seed=None):
         """Plain decoding of the whole batch through the same engine (one row per sample per block).  With a processor list or
         sampling every token is picked on the host from the sample's logits row (forward-only step + la_llama_bcommit).
         `stopping_criteria`: the caller's criteria besides the length bound (MaxTimeCriteria, custom ones) are evaluated per
@@ -544,18 +562,28 @@ class LookaheadPreTrainedModel(object):
         multi = bool(getattr(eng, 'max_blocks', 0))
         # exactly one repetition penalty: the device stage of lookahead_generation, every slot seeded with its padded row
         dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample, enabled=device_processors) if host_pick else None
-        if dev_penalty is not None:
+        # a do_sample request with an int sample_seed whose list device_sampling accepts: the sampling stage (stream = batch index)
+        dev_sample = device_sampling(logits_processor, eng, do_sample=do_sample, seed=sample_seed, enabled=device_processors) if host_pick else None
+        if dev_sample is not None:
+            dev_penalty = dev_sample['penalty']
+        if dev_penalty is not None or dev_sample is not None:
             host_pick = False
         try:
             if dev_penalty is not None:
                 eng.set_repetition_penalty(dev_penalty)
                 for i in range(bs):
                     eng.seed_penalty_context(i, ids0[i].tolist())
+            if dev_sample is not None:
+                for i in range(bs):
+                    eng.sampling_stream(i, i)
+                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
             return self._greedy_search(eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length,
                                        eos, pad_token_id, input_ids.device)
         finally:
             if dev_penalty is not None:
                 eng.set_repetition_penalty(1.0)
+            if dev_sample is not None:
+                eng.set_sampling(False)
 
     def _greedy_search(self, eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length, eos,
                        pad_token_id, out_device):
@@ -625,7 +653,11 @@ class LookaheadPreTrainedModel(object):
         dk = ga.decoding_kwargs
         if dk.get('use_lookahead', False) and dk.get('decoding_length', 64) > 1 and dk.get('branch_length', 12) > 0:
             dk['do_sample'] = ga.do_sample
-            return self.lookahead_generation(input_ids, logits_processor=ga.logits_processor if len(ga.logits_processor) else None,
+            la_procs = ga.logits_processor
+            if ga.do_sample and 'sample_seed' in dk:         # opt-in: the config-derived warpers reach the lookahead branch too
+                from transformers import LogitsProcessorList
+                la_procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
+            return self.lookahead_generation(input_ids, logits_processor=la_procs if len(la_procs) else None,
                                              stopping_criteria=ga.stopping_criteria, pad_token_id=ga.pad_token_id,
                                              eos_token_id=ga.eos_token_id, return_dict_in_generate=ga.return_dict_in_generate,
                                              streamer=streamer, attention_mask=attention_mask, decoding_kwargs=dk)
@@ -636,5 +668,6 @@ class LookaheadPreTrainedModel(object):
                                  else getattr(self.generation_config, 'eos_token_id', None),
                                  pad_token_id=ga.pad_token_id if ga.pad_token_id is not None else 0,
                                  logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
-                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True))
+                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True),
+                                 sample_seed=dk.get('sample_seed', None))
         return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out
