@@ -1,8 +1,16 @@
 # -*- coding: utf-8 -*-
-"""API types of the lookahead path (mirror of lookahead/lookahead/common/lookahead_generation_utils.py:19-76)."""
+"""API types of the lookahead path (mirror of lookahead/lookahead/common/lookahead_generation_utils.py:19-76) and the front end the
+single-sequence and the batch loop share (pretrained_model.py, pretrained_model_batch.py): the device-stage scope, the host token
+pick, the request prologue and the body of generate()."""
+import gc
+import warnings
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from enum import Enum
 from typing import Any, Dict, Optional, Tuple
+
+import numpy as np
+import torch
 
 
 class GenerationMode(str, Enum):
@@ -118,6 +126,162 @@ def device_sampling(logits_processor, engine, do_sample=False, seed=None, enable
                 out['top_p'] = float(p)
         at += 1
     return out
+
+
+def plan_device_stages(logits_processor, engine, eligible, do_sample=False, seed=None, enabled=True):
+    """Which device stages serve this request: None (-> the host pick) or {'penalty': float | None, 'sampling': dict | None}, the
+    answers of device_repetition_penalty / device_sampling with the sampling list's own penalty folded in.  `eligible`: the loop's
+    own conditions (no scores, no wide tree, no sharded job, no device trie, ...), which differ between the loops."""
+    if not eligible:
+        return None
+    penalty = device_repetition_penalty(logits_processor, engine, do_sample=do_sample, enabled=enabled)
+    sampling = device_sampling(logits_processor, engine, do_sample=do_sample, seed=seed, enabled=enabled)
+    if sampling is not None:
+        penalty = sampling['penalty']
+    if penalty is None and sampling is None:
+        return None
+    return {'penalty': penalty, 'sampling': sampling}
+
+
+@contextmanager
+def device_stages(engine, plan, slots):
+    """The stages of `plan` (plan_device_stages; None: nothing) switched on for one request and off again, also after an exception:
+    the next request starts without them.  slots: (slot, sampling stream word, token row the slot's penalty context is seeded
+    with) per sequence — the batch loops seed with the padded row (what the reference's walk hands the processor); row None: the
+    prefill seeds the context with the prompt itself."""
+    penalty, sampling = (None, None) if plan is None else (plan['penalty'], plan['sampling'])
+    try:
+        if penalty is not None:
+            engine.set_repetition_penalty(penalty)
+            for slot, _, row in slots:
+                if row is not None:
+                    engine.seed_penalty_context(slot, row)
+        if sampling is not None:
+            for slot, stream, _ in slots:
+                engine.sampling_stream(slot, stream)
+            engine.set_sampling(True, sampling['seed'], sampling['temperature'], sampling['top_k'], sampling['top_p'])
+        yield
+    finally:
+        if penalty is not None:
+            engine.set_repetition_penalty(1.0)
+        if sampling is not None:
+            engine.set_sampling(False)
+
+
+def pick_token(logits_processor, do_sample, ctx_ids, logits_row, device):
+    """Next token from one logits row through the processor list (pretrained_model.py:833-839, pretrained_model_batch.py:840-846):
+    -> (token, processed scores [1, vocab]).  The scores may alias the engine's logits buffer: a caller that keeps them clones."""
+    sc = logits_row[None]
+    if logits_processor is not None and len(logits_processor) > 0:
+        sc = logits_processor(torch.tensor([ctx_ids], dtype=torch.long, device=device), sc.clone())
+    if do_sample:
+        return int(torch.multinomial(torch.softmax(sc.float(), dim=-1), num_samples=1)[0, 0]), sc
+    return int(torch.argmax(sc, dim=-1)[0]), sc
+
+
+def _parents_of(rowmask, T):
+    """parent row of every tree row = highest set bit below the row over the concatenated ancestor words (DFS order)"""
+    rm = np.asarray(rowmask, dtype=np.uint64)
+    if rm.ndim == 1:
+        rm = rm[:, None]
+    parent = [-1] * T
+    for j in range(1, T):
+        below = 0
+        for w in range(rm.shape[1]):
+            below |= int(rm[j, w]) << (64 * w)
+        below &= (1 << j) - 1
+        parent[j] = below.bit_length() - 1
+    return parent
+
+
+def _max_length_of(stopping_criteria, max_length):
+    if max_length is not None:
+        warnings.warn("`max_length` is deprecated in this function, use "
+                      "`stopping_criteria=StoppingCriteriaList([MaxLengthCriteria(max_length=max_length)])` instead.",
+                      UserWarning)
+        return int(max_length)
+    if stopping_criteria is None:
+        return None
+    ml = getattr(stopping_criteria, 'max_length', None)
+    if ml is None and isinstance(stopping_criteria, int):
+        ml = stopping_criteria
+    return None if ml is None else int(ml)
+
+
+def _custom_stop(stopping_criteria):
+    """The user's criteria besides MaxLengthCriteria as one predicate stop(token_row) -> bool, or None when there are none.
+    The reference evaluates `stopping_criteria(input_ids, scores)` after every verify step (pretrained_model.py:1225-1226;
+    batch: once per sample on input_ids[i:i+1, :cur+1], pretrained_model_batch.py:1284); scores = the tuple collected so far under
+    output_scores, else None.  The length criterion itself is the `len(seq) >= max_length` test of the loops."""
+    if stopping_criteria is None or isinstance(stopping_criteria, int) or not callable(stopping_criteria):
+        return None
+    try:
+        crit = list(stopping_criteria)
+    except TypeError:
+        crit = [stopping_criteria]
+    crit = [c for c in crit if type(c).__name__ != 'MaxLengthCriteria']
+    if not crit:
+        return None
+
+    def stop(token_row, device='cpu', scores=None):
+        ids = torch.tensor([list(token_row)], dtype=torch.long, device=device)
+        for c in crit:
+            r = c(ids, scores)
+            if bool(r.any()) if torch.is_tensor(r) else bool(r):
+                return True
+        return False
+    return stop
+
+
+@contextmanager
+def gc_paused():
+    """The step loops run with the cyclic garbage collector paused: a generation-2 pass over torch's object graph stalls the host
+    thread for tens of ms (measured 37 ms = 9 verify steps) and the loops create no reference cycles."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
+
+
+def begin_request(model, logits_processor, stopping_criteria, max_length, pad_token_id, eos_token_id, output_attentions,
+                  output_hidden_states, output_scores, return_dict_in_generate, model_kwargs):
+    """What both lookahead_generation loops settle before they touch the engine: the processor list wrapped, whether it (or sampling)
+    asks for the sequential accept path, pad / eos / return_dict_in_generate / output_scores resolved against the
+    model's generation_config, the trie cache created and given its eos ids and stop words, the per-request lists of
+    decoding_kwargs emptied and the length bound read.
+    -> (logits_processor, sequential, pad_token_id, eos_token_id, return_dict_in_generate, scores, decoding_kwargs, stop_max_length);
+    `scores` is () when the request returns scores (return_dict_in_generate and output_scores), else None."""
+    if isinstance(logits_processor, (list, tuple)) and not callable(logits_processor):
+        from transformers import LogitsProcessorList      # a plain list of processors: the reference's generate() wraps it the same way
+        logits_processor = LogitsProcessorList(list(logits_processor))
+    sequential = (logits_processor is not None and len(logits_processor) > 0) or \
+        bool(model_kwargs.get('decoding_kwargs', {}).get('do_sample', False))
+    if output_attentions or output_hidden_states:
+        raise NotImplementedError('attentions / hidden_states are intermediates the device path never materialises '
+                                  '(fused attention, activations in MFMA fragment order); scores are returned (output_scores)')
+    cfg = model.generation_config
+    pad_token_id = pad_token_id if pad_token_id is not None else getattr(cfg, 'pad_token_id', None)
+    eos_token_id = eos_token_id if eos_token_id is not None else getattr(cfg, 'eos_token_id', None)
+    if isinstance(eos_token_id, int):
+        eos_token_id = [eos_token_id]
+    return_dict_in_generate = bool(return_dict_in_generate) if return_dict_in_generate is not None \
+        else bool(getattr(cfg, 'return_dict_in_generate', False))
+    output_scores = bool(output_scores) if output_scores is not None else bool(getattr(cfg, 'output_scores', False))
+    scores = () if (return_dict_in_generate and output_scores) else None
+    if not hasattr(model, 'lookahead_cache') or model.lookahead_cache is None:
+        from .lookahead_cache import LookaheadCache
+        model.lookahead_cache = LookaheadCache()
+    decoding_kwargs = model_kwargs['decoding_kwargs']
+    model.lookahead_cache.eos_ids = eos_token_id
+    model.lookahead_cache.stop_words = decoding_kwargs.get('stop_words', {})
+    decoding_kwargs.update({'edls': [], 'dls': [], 'fts': [], 'qts': []})
+    stop_max_length = _max_length_of(stopping_criteria, max_length)
+    if stop_max_length is None:
+        raise ValueError('lookahead_generation needs a MaxLengthCriteria (stopping_criteria.max_length)')
+    return logits_processor, sequential, pad_token_id, eos_token_id, return_dict_in_generate, scores, decoding_kwargs, stop_max_length
 
 
 # ---------------------------------------------------------------------------------------------------- generate() front door
@@ -249,3 +413,51 @@ def resolve_generate_args(model_generation_config, input_length, generation_conf
                       return_dict_in_generate=bool(val['return_dict_in_generate']), output_scores=bool(val['output_scores']),
                       logits_processor=procs, logits_warper=warpers, stopping_criteria=crit, decoding_kwargs=dk)
     return ga, kwargs
+
+
+def _get_generation_mode(decoding_kwargs):
+    """pretrained_model.py:55-106 reduced to the two modes this path serves."""
+    dk = decoding_kwargs or {}
+    if dk.get('use_lookahead', False) and dk.get('decoding_length', 64) > 1 and dk.get('branch_length', 12) > 0:
+        return GenerationMode.LOOKAHEAD_GENERATION
+    return GenerationMode.GREEDY_SEARCH
+
+
+def run_generate(model, batch, inputs, generation_config, logits_processor, stopping_criteria, prefix_allowed_tokens_fn,
+                 assistant_model, streamer, kwargs):
+    """The body of both generate() methods: resolve the arguments, then dispatch to model.lookahead_generation or
+    model.greedy_search.  `batch`: the plain leg takes attention_mask / pad_token_id; the single-sequence model records
+    dk['generation_mode'] and forwards output_scores to its lookahead loop, the batch model does neither."""
+    from transformers import LogitsProcessorList
+    if prefix_allowed_tokens_fn is not None or assistant_model is not None:
+        raise NotImplementedError('prefix_allowed_tokens_fn / assistant_model: outside the lookahead path (SURVEY section 2, out of scope)')
+    input_ids = inputs if inputs is not None else kwargs.pop('input_ids', None)
+    kwargs.pop('input_ids', None)
+    if input_ids is None:
+        raise ValueError('generate() needs input_ids')
+    ga, model_kwargs = resolve_generate_args(model.generation_config, input_ids.size(1), generation_config=generation_config,
+                                             logits_processor=logits_processor, stopping_criteria=stopping_criteria,
+                                             device=getattr(getattr(model, 'engine', None), 'device', None), **kwargs)
+    attention_mask = model_kwargs.pop('attention_mask', None)
+    dk = ga.decoding_kwargs
+    if _get_generation_mode(dk) == GenerationMode.LOOKAHEAD_GENERATION:      # the loops feed the streamer themselves (prompt first, :318-319)
+        dk['do_sample'] = ga.do_sample
+        extra = {}
+        if not batch:
+            dk['generation_mode'] = GenerationMode.LOOKAHEAD_GENERATION
+            extra['output_scores'] = ga.output_scores or None
+        la_procs = ga.logits_processor
+        if ga.do_sample and 'sample_seed' in dk:         # opt-in: the config-derived warpers reach the lookahead branch too
+            la_procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
+        return model.lookahead_generation(input_ids, logits_processor=la_procs if len(la_procs) else None,
+                                          stopping_criteria=ga.stopping_criteria, pad_token_id=ga.pad_token_id,
+                                          eos_token_id=ga.eos_token_id, return_dict_in_generate=ga.return_dict_in_generate,
+                                          streamer=streamer, attention_mask=attention_mask, decoding_kwargs=dk, **extra)
+    procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
+    extra = {'attention_mask': attention_mask, 'pad_token_id': ga.pad_token_id if ga.pad_token_id is not None else 0} if batch else {}
+    out = model.greedy_search(input_ids, ga.max_length, eos_token_id=ga.eos_token_id if ga.eos_token_id is not None
+                              else getattr(model.generation_config, 'eos_token_id', None),
+                              logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
+                              stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True),
+                              sample_seed=dk.get('sample_seed', None), **extra)
+    return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out

@@ -11,16 +11,13 @@ from .lookahead_cache import LookaheadCache
 from .pretrained_model import LookaheadPreTrainedModel
 
 
-class LlamaForCausalLM(LookaheadPreTrainedModel):
-    def __init__(self, shape, state_dict, max_length=2048, device='cuda:0', eos_token_id=2, pad_token_id=0,
-                 attn_split=0, gemm_cfg=None, consume_state_dict=False, balanced=True, fuse=0, max_blocks=0, kv_ring=False, dtype=None,
-                 weight_format=None):
+class _LlamaWrapper(object):
+    """What the single-sequence and the batch wrapper share: the constructors from a transformers model / a checkpoint directory /
+    random weights, and the nn.Module-style surface the reference scripts call on a loaded model.  A subclass's __init__ creates
+    self.engine and calls _finish_init."""
+
+    def _finish_init(self, shape, device, eos_token_id, pad_token_id):
         self.shape = shape
-        # weight_format='fp8': W8A16 projections (LlamaVerifyEngine); a state dict of float8_e4m3fn projections selects it by itself
-        self.engine = LlamaVerifyEngine(shape, state_dict, max_length=max_length, device=device,
-                                        attn_split=attn_split, gemm_cfg=gemm_cfg,
-                                        consume_state_dict=consume_state_dict, balanced=balanced, fuse=fuse,
-                                        max_blocks=max_blocks, kv_ring=kv_ring, dtype=dtype, weight_format=weight_format)
         self.generation_config = SimpleNamespace(eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                                                  return_dict_in_generate=False)
         self.config = SimpleNamespace(is_encoder_decoder=False, vocab_size=shape.vocab)
@@ -29,8 +26,8 @@ class LlamaForCausalLM(LookaheadPreTrainedModel):
 
     @classmethod
     def _shape_of(cls, cfg, kw):
-        """LlamaShape of a transformers config.  Family wrappers (modeling_mixtral.py) override this to check the checkpoint's family and to
-        consume their own keywords (sliding_window=...) from kw before the engine sees it."""
+        """LlamaShape of a transformers config.  Family wrappers (modeling_mixtral.py, modeling_qwen2.py) override this to check the
+        checkpoint's family and to consume their own keywords (sliding_window=...) from kw before the engine sees it."""
         return LlamaShape.from_hf(cfg)
 
     @classmethod
@@ -88,3 +85,15 @@ class LlamaForCausalLM(LookaheadPreTrainedModel):
     def random_init(cls, shape, seed=0, device='cuda:0', decisive=False, **kw):
         return cls(shape, random_weights(shape, seed=seed, device=device, decisive=decisive), device=device,
                    consume_state_dict=True, **kw)
+
+
+class LlamaForCausalLM(_LlamaWrapper, LookaheadPreTrainedModel):
+    def __init__(self, shape, state_dict, max_length=2048, device='cuda:0', eos_token_id=2, pad_token_id=0,
+                 attn_split=0, gemm_cfg=None, consume_state_dict=False, balanced=True, fuse=0, max_blocks=0, kv_ring=False, dtype=None,
+                 weight_format=None):
+        # weight_format='fp8': W8A16 projections (LlamaVerifyEngine); a state dict of float8_e4m3fn projections selects it by itself
+        self.engine = LlamaVerifyEngine(shape, state_dict, max_length=max_length, device=device,
+                                        attn_split=attn_split, gemm_cfg=gemm_cfg,
+                                        consume_state_dict=consume_state_dict, balanced=balanced, fuse=fuse,
+                                        max_blocks=max_blocks, kv_ring=kv_ring, dtype=dtype, weight_format=weight_format)
+        self._finish_init(shape, device, eos_token_id, pad_token_id)

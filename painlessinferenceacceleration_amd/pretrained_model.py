@@ -8,16 +8,14 @@ accepted tokens) and one native trie update (la_cache_stream_put).  The referenc
 synchronisations per step become one.
 """
 import time
-import warnings
 from threading import Thread
 
 import numpy as np
 import torch
 
 from . import _lib
-from .lookahead_cache import LookaheadCache
-from .lookahead_generation_utils import (GenerationMode, LookaheadDecoderOnlyOutput, device_repetition_penalty,
-                                          device_sampling, resolve_generate_args)
+from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, _custom_stop, _max_length_of, _parents_of,  # noqa: F401
+                                          begin_request, device_stages, gc_paused, pick_token, plan_device_stages, run_generate)
 
 _ONE = np.array([1], dtype=np.uint64)
 
@@ -33,60 +31,6 @@ def _pack_rows(mask, W=None):
         if cols.shape[1]:
             out[:, w] = (cols << np.arange(cols.shape[1], dtype=np.uint64)[None, :]).sum(axis=1).astype(np.uint64)
     return out[:, 0] if W == 1 else out
-
-
-def _parents_of(rowmask, T):
-    """parent row of every tree row = highest set bit below the row over the concatenated ancestor words (DFS order)"""
-    rm = np.asarray(rowmask, dtype=np.uint64)
-    if rm.ndim == 1:
-        rm = rm[:, None]
-    parent = [-1] * T
-    for j in range(1, T):
-        below = 0
-        for w in range(rm.shape[1]):
-            below |= int(rm[j, w]) << (64 * w)
-        below &= (1 << j) - 1
-        parent[j] = below.bit_length() - 1
-    return parent
-
-
-def _max_length_of(stopping_criteria, max_length):
-    if max_length is not None:
-        warnings.warn("`max_length` is deprecated in this function, use "
-                      "`stopping_criteria=StoppingCriteriaList([MaxLengthCriteria(max_length=max_length)])` instead.",
-                      UserWarning)
-        return int(max_length)
-    if stopping_criteria is None:
-        return None
-    ml = getattr(stopping_criteria, 'max_length', None)
-    if ml is None and isinstance(stopping_criteria, int):
-        ml = stopping_criteria
-    return None if ml is None else int(ml)
-
-
-def _custom_stop(stopping_criteria):
-    """The user's criteria besides MaxLengthCriteria as one predicate stop(token_row) -> bool, or None when there are none.
-    The reference evaluates `stopping_criteria(input_ids, scores)` after every verify step (pretrained_model.py:1225-1226;
-    batch: once per sample on input_ids[i:i+1, :cur+1], pretrained_model_batch.py:1284); scores = the tuple collected so far under
-    output_scores, else None.  The length criterion itself is the `len(seq) >= max_length` test of the loops."""
-    if stopping_criteria is None or isinstance(stopping_criteria, int) or not callable(stopping_criteria):
-        return None
-    try:
-        crit = list(stopping_criteria)
-    except TypeError:
-        crit = [stopping_criteria]
-    crit = [c for c in crit if type(c).__name__ != 'MaxLengthCriteria']
-    if not crit:
-        return None
-
-    def stop(token_row, device='cpu', scores=None):
-        ids = torch.tensor([list(token_row)], dtype=torch.long, device=device)
-        for c in crit:
-            r = c(ids, scores)
-            if bool(r.any()) if torch.is_tensor(r) else bool(r):
-                return True
-        return False
-    return stop
 
 
 class LookaheadPreTrainedModel(object):
@@ -159,17 +103,10 @@ class LookaheadPreTrainedModel(object):
     # ---------------------------------------------------------------------------------------------- the loop
     @torch.no_grad()
     def lookahead_generation(self, *args, **kwargs):
-        """Entry point (signature of the reference's lookahead_generation, see _lookahead_generation).  The step loop
-        runs with the cyclic garbage collector paused: a generation-2 pass over torch's object graph stalls the host
-        thread for tens of ms (measured 37 ms = 9 verify steps) and the loop creates no reference cycles."""
-        import gc
-        was_enabled = gc.isenabled()
-        gc.disable()
-        try:
+        """Entry point (signature of the reference's lookahead_generation, see _lookahead_generation); the step loop runs with
+        the cyclic garbage collector paused (gc_paused)."""
+        with gc_paused():
             return self._lookahead_generation(*args, **kwargs)
-        finally:
-            if was_enabled:
-                gc.enable()
 
     def _lookahead_generation(self, input_ids, logits_processor=None, stopping_criteria=None, max_length=None,
                              pad_token_id=None, eos_token_id=None, output_attentions=None,
@@ -178,39 +115,15 @@ class LookaheadPreTrainedModel(object):
         # processors are applied sequentially along the accepted path (pretrained_model.py:834), so a non-empty
         # list (or sampling) takes the host-walked path: device forward only (mode 2), one logits row per accepted token,
         # host-decided commit.  The empty-list greedy default stays entirely on the device.
-        if isinstance(logits_processor, (list, tuple)) and not callable(logits_processor):
-            from transformers import LogitsProcessorList      # a plain list of processors: the reference's generate() wraps it the same way
-            logits_processor = LogitsProcessorList(list(logits_processor))
-        sequential = (logits_processor is not None and len(logits_processor) > 0) or \
-            bool(model_kwargs.get('decoding_kwargs', {}).get('do_sample', False))
-        if output_attentions or output_hidden_states:
-            raise NotImplementedError('attentions / hidden_states are intermediates the device path never materialises '
-                                      '(fused attention, activations in MFMA fragment order); scores are returned (output_scores)')
-        gc = self.generation_config
-        pad_token_id = pad_token_id if pad_token_id is not None else getattr(gc, 'pad_token_id', None)
-        eos_token_id = eos_token_id if eos_token_id is not None else getattr(gc, 'eos_token_id', None)
-        if isinstance(eos_token_id, int):
-            eos_token_id = [eos_token_id]
-        return_dict_in_generate = bool(return_dict_in_generate) if return_dict_in_generate is not None \
-            else bool(getattr(gc, 'return_dict_in_generate', False))
-        output_scores = bool(output_scores) if output_scores is not None else bool(getattr(gc, 'output_scores', False))
         # `scores` as the reference returns them (pretrained_model.py:1092, 1195, 1208-1209): ONE entry per verify step, and that entry
         # is model_kwargs['next_tokens_scores'] — which only the no-draft branch writes (:795: the prefill and steps whose retrieval
         # came back empty).  A step WITH drafts therefore appends the previous no-draft step's tensor again (pinned on
         # tests/golden/llama_tiny_scores_fp32.npz).  decoding_kwargs['fresh_scores'] = True (an extension) appends, on draft steps,
         # the processed logits row the step's LAST emitted token was picked from instead.
-        scores = () if (return_dict_in_generate and output_scores) else None
-
-        if not hasattr(self, 'lookahead_cache') or self.lookahead_cache is None:
-            self.lookahead_cache = LookaheadCache()
-        decoding_kwargs = model_kwargs['decoding_kwargs']
-        self.lookahead_cache.eos_ids = eos_token_id
-        self.lookahead_cache.stop_words = decoding_kwargs.get('stop_words', {})
-        decoding_kwargs.update({'eos': eos_token_id[0] if eos_token_id is not None else 2,
-                                'edls': [], 'dls': [], 'fts': [], 'qts': []})
-        stop_max_length = _max_length_of(stopping_criteria, max_length)
-        if stop_max_length is None:
-            raise ValueError('lookahead_generation needs a MaxLengthCriteria (stopping_criteria.max_length)')
+        logits_processor, sequential, pad_token_id, eos_token_id, return_dict_in_generate, scores, decoding_kwargs, stop_max_length = \
+            begin_request(self, logits_processor, stopping_criteria, max_length, pad_token_id, eos_token_id, output_attentions,
+                          output_hidden_states, output_scores, return_dict_in_generate, model_kwargs)
+        decoding_kwargs['eos'] = eos_token_id[0] if eos_token_id is not None else 2
         decoding_length = decoding_kwargs.get('decoding_length', 64)
         # trees wider than one 64-row block run as consecutive blocks of one multi-block pass (eng.tstep; the reference's best
         # published setting is decoding_length=128, branch_length=32, lookahead/README.md:100)
@@ -271,20 +184,13 @@ class LookaheadPreTrainedModel(object):
         # a list that is exactly one RepetitionPenaltyLogitsProcessor runs as a stage of the device step (the penalised argmax of
         # every tree row, then the fused accept walk: csrc/la_penalty.hip) and keeps the graph, the fused tail and the native loop;
         # every other list, sampling, scores, wide trees, the device trie and sharded jobs keep the host walk below
-        dev_penalty = None
-        if sequential and scores is None and not wide and gather is None and not decoding_kwargs.get('device_trie', False):
-            dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample,
-                                                    enabled=decoding_kwargs.get('device_processors', True))
         # a do_sample request that names decoding_kwargs['sample_seed'] and whose list is [repetition penalty?] + [temperature?,
         # top-k?, top-p?] runs as the sampling stage of the device step (csrc/la_sample.hip: the seeded draw of every tree row,
         # then the same accept walk) under the same conditions; without the key it takes the host walk exactly as before
-        dev_sample = None
-        if sequential and scores is None and not wide and gather is None and not decoding_kwargs.get('device_trie', False):
-            dev_sample = device_sampling(logits_processor, eng, do_sample=do_sample, seed=decoding_kwargs.get('sample_seed', None),
-                                         enabled=decoding_kwargs.get('device_processors', True))
-        if dev_sample is not None:
-            dev_penalty = dev_sample['penalty']
-        if dev_penalty is not None or dev_sample is not None:
+        stages = plan_device_stages(logits_processor, eng, sequential and scores is None and not wide and gather is None
+                                    and not decoding_kwargs.get('device_trie', False), do_sample=do_sample,
+                                    seed=decoding_kwargs.get('sample_seed', None), enabled=decoding_kwargs.get('device_processors', True))
+        if stages is not None:
             sequential = False
         native_loop = (not sequential and streamer is None and dm.split('_')[0] == 'hier' and not wide
                        and custom_stop is None and gather is None and scores is None
@@ -295,139 +201,126 @@ class LookaheadPreTrainedModel(object):
                        and hasattr(eng, 'decode_native'))
 
         def pick(scores_ids, row):
-            """next token from one logits row through the processor list (pretrained_model.py:833-839)"""
-            ctx = torch.tensor([scores_ids], dtype=torch.long, device=eng.device)
             lg = eng.mlogits() if wide else eng.logits()
-            sc = logits_processor(ctx, lg[row][None].clone()) if logits_processor is not None and \
-                len(logits_processor) > 0 else lg[row][None]
+            tok, sc = pick_token(logits_processor, do_sample, scores_ids, lg[row], eng.device)
             if scores is not None:
                 picked[0] = sc.clone()
-            if do_sample:
-                return int(torch.multinomial(torch.softmax(sc.float(), dim=-1), num_samples=1)[0, 0])
-            return int(torch.argmax(sc, dim=-1)[0])
+            return tok
 
         picked = [None]            # scores of the last pick() call
         last_scores = None         # what the reference's model_kwargs['next_tokens_scores'] holds
         flushed = False
         try:
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(dev_penalty)      # prefill seeds the context set with the prompt
-            if dev_sample is not None:
-                eng.sampling_stream(0, 0)
-                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
-            while True:
-                if first:
-                    host_row = sequential or scores is not None      # the last prompt row's logits must stay readable
-                    if wide:
-                        tok = eng.mprefill(0, seq)
-                        row = (len(seq) - 1) % (64 * eng.max_blocks)
-                    else:
-                        tok = eng.prefill(seq, fast=False) if host_row else eng.prefill(seq)
-                        row = (len(seq) - 1) % 64
-                    if host_row:
-                        t = pick(seq, row)                           # sequential: THE pick; otherwise the same argmax, taken for its scores
-                        next_tokens = [t] if sequential else [tok]
-                    else:
-                        next_tokens = [tok]
-                    last_scores = picked[0]
-                    decoding_kwargs['dls'].append(1)
-                    decoding_kwargs['edls'].append(1)
-                    first = False
-                else:
-                    ids, rowmask = self.lookahead_prepare_inputs_for_generation(seq, decoding_kwargs, len(seq))
-                    if len(ids) == 0:
-                        ids, rowmask = np.asarray(seq[-1:], dtype=np.int32), _ONE
-                    if sequential:
-                        T = len(ids)
+            with device_stages(eng, stages, [(0, 0, None)]):      # (row None: prefill seeds the penalty context with the prompt)
+                while True:
+                    if first:
+                        host_row = sequential or scores is not None      # the last prompt row's logits must stay readable
                         if wide:
-                            eng.tstep(ids, rowmask, mode=2)
+                            tok = eng.mprefill(0, seq)
+                            row = (len(seq) - 1) % (64 * eng.max_blocks)
                         else:
-                            eng.verify_only(ids, rowmask)
-                        parent = _parents_of(rowmask, T)
-                        # every row whose parent is live and whose token was picked stays live; the first one supplies the
-                        # next logits row (the reference's surviving leaf branches, pretrained_model.py:831, 850-860: in a
-                        # par layout a shared prefix is duplicated across chains and the walk may move to a later chain)
-                        cur, live, rows, next_tokens = 0, {0}, [0], []
-                        while True:
-                            t = pick(seq + next_tokens, cur)
-                            next_tokens.append(t)
-                            nxt = [j for j in range(1, T) if parent[j] in live and int(ids[j]) == t]
-                            if not nxt:
-                                break
-                            cur, live = nxt[0], set(nxt)
-                            rows.append(cur)
-                        if wide:
-                            eng.tcommit(rows, T)
+                            tok = eng.prefill(seq, fast=False) if host_row else eng.prefill(seq)
+                            row = (len(seq) - 1) % 64
+                        if host_row:
+                            t = pick(seq, row)                           # sequential: THE pick; otherwise the same argmax, taken for its scores
+                            next_tokens = [t] if sequential else [tok]
                         else:
-                            eng.commit(rows)
-                    elif wide:
-                        next_tokens, _ = eng.tstep(ids, rowmask, mode=0)
-                    elif gather is not None and hasattr(eng, 'step_async'):
-                        eng.step_async(ids, rowmask, mode=0)
-                        gather.overlap(self.lookahead_cache, branch_length)      # split-phase: the previous step's gather + puts, under this pass
-                        next_tokens, _ = eng.step_finish()
+                            next_tokens = [tok]
+                        last_scores = picked[0]
+                        decoding_kwargs['dls'].append(1)
+                        decoding_kwargs['edls'].append(1)
+                        first = False
                     else:
-                        next_tokens, _ = eng.step(ids, rowmask, mode=0)
-                    if scores is not None:
+                        ids, rowmask = self.lookahead_prepare_inputs_for_generation(seq, decoding_kwargs, len(seq))
+                        if len(ids) == 0:
+                            ids, rowmask = np.asarray(seq[-1:], dtype=np.int32), _ONE
                         if sequential:
-                            if len(ids) <= 1 or fresh_scores:        # no-draft step (:783-795) — or every step (extension)
-                                last_scores = picked[0]
-                        elif len(ids) <= 1:
-                            # device-accepted step without drafts: the block's only logits row, through the (empty) processor list
-                            lg = eng.mlogits() if wide else eng.logits()
-                            last_scores = lg[0][None].clone()
-                    decoding_kwargs['dls'].append(len(ids))
-                    decoding_kwargs['edls'].append(len(next_tokens))
-                    if decoding_kwargs.get('debug_lookahead', False):
-                        tok = decoding_kwargs.get('tokenizer', None)
-                        words = '' if tok is None else tok.decode(next_tokens)
-                        print(f'decoding_length:{len(ids)} accept_length:{len(next_tokens)} '
-                              f'query:{decoding_kwargs["decoding_qids"]} hits:{decoding_kwargs["sizes"]} '
-                              f'accept_token:{next_tokens} accept_word:{words}')
-                seq.extend(next_tokens)
-                if scores is not None:
-                    scores += (last_scores,)
-                if streamer is not None:
-                    streamer.put(np.array([next_tokens]))
-                finished = len(seq) >= stop_max_length or any(t in eos_set for t in next_tokens) or \
-                    (custom_stop is not None and custom_stop(seq, out_device, scores))           # :1225-1231
-                if gather is not None:
-                    gather.step_update(self.lookahead_cache, next_tokens, branch_length, done=finished)
-                else:
-                    self.lookahead_cache.stream_put(next_tokens, branch_length=branch_length + 1, final=False,
-                                                    mode='output', idx=0)
-                te = time.time()
-                decoding_kwargs['fts'].append(te - ts)
-                ts = te
-                if finished:
+                            T = len(ids)
+                            if wide:
+                                eng.tstep(ids, rowmask, mode=2)
+                            else:
+                                eng.verify_only(ids, rowmask)
+                            parent = _parents_of(rowmask, T)
+                            # every row whose parent is live and whose token was picked stays live; the first one supplies the
+                            # next logits row (the reference's surviving leaf branches, pretrained_model.py:831, 850-860: in a
+                            # par layout a shared prefix is duplicated across chains and the walk may move to a later chain)
+                            cur, live, rows, next_tokens = 0, {0}, [0], []
+                            while True:
+                                t = pick(seq + next_tokens, cur)
+                                next_tokens.append(t)
+                                nxt = [j for j in range(1, T) if parent[j] in live and int(ids[j]) == t]
+                                if not nxt:
+                                    break
+                                cur, live = nxt[0], set(nxt)
+                                rows.append(cur)
+                            if wide:
+                                eng.tcommit(rows, T)
+                            else:
+                                eng.commit(rows)
+                        elif wide:
+                            next_tokens, _ = eng.tstep(ids, rowmask, mode=0)
+                        elif gather is not None and hasattr(eng, 'step_async'):
+                            eng.step_async(ids, rowmask, mode=0)
+                            gather.overlap(self.lookahead_cache, branch_length)      # split-phase: the previous step's gather + puts, under this pass
+                            next_tokens, _ = eng.step_finish()
+                        else:
+                            next_tokens, _ = eng.step(ids, rowmask, mode=0)
+                        if scores is not None:
+                            if sequential:
+                                if len(ids) <= 1 or fresh_scores:        # no-draft step (:783-795) — or every step (extension)
+                                    last_scores = picked[0]
+                            elif len(ids) <= 1:
+                                # device-accepted step without drafts: the block's only logits row, through the (empty) processor list
+                                lg = eng.mlogits() if wide else eng.logits()
+                                last_scores = lg[0][None].clone()
+                        decoding_kwargs['dls'].append(len(ids))
+                        decoding_kwargs['edls'].append(len(next_tokens))
+                        if decoding_kwargs.get('debug_lookahead', False):
+                            tok = decoding_kwargs.get('tokenizer', None)
+                            words = '' if tok is None else tok.decode(next_tokens)
+                            print(f'decoding_length:{len(ids)} accept_length:{len(next_tokens)} '
+                                  f'query:{decoding_kwargs["decoding_qids"]} hits:{decoding_kwargs["sizes"]} '
+                                  f'accept_token:{next_tokens} accept_word:{words}')
+                    seq.extend(next_tokens)
+                    if scores is not None:
+                        scores += (last_scores,)
+                    if streamer is not None:
+                        streamer.put(np.array([next_tokens]))
+                    finished = len(seq) >= stop_max_length or any(t in eos_set for t in next_tokens) or \
+                        (custom_stop is not None and custom_stop(seq, out_device, scores))           # :1225-1231
                     if gather is not None:
-                        gather.drain(self.lookahead_cache, branch_length)          # until every rank's sequence has finished
-                        gather.flush(self.lookahead_cache, branch_length)
+                        gather.step_update(self.lookahead_cache, next_tokens, branch_length, done=finished)
                     else:
+                        self.lookahead_cache.stream_put(next_tokens, branch_length=branch_length + 1, final=False,
+                                                        mode='output', idx=0)
+                    te = time.time()
+                    decoding_kwargs['fts'].append(te - ts)
+                    ts = te
+                    if finished:
+                        if gather is not None:
+                            gather.drain(self.lookahead_cache, branch_length)          # until every rank's sequence has finished
+                            gather.flush(self.lookahead_cache, branch_length)
+                        else:
+                            self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=0)
+                        flushed = True
+                        break
+                    if native_loop:
+                        # every remaining step runs in la_lookahead_decode: same calls in the same order (hier_get -> la_llama_step
+                        # -> stream_put -> stop checks), without the interpreter between them
+                        new, dls_, edls_, fts_, qts_, fin = eng.decode_native(
+                            self.lookahead_cache, seq, stop_max_length, eos_ids=eos_set, decoding_length=decoding_length,
+                            branch_length=branch_length, max_query_length=decoding_kwargs.get('max_query_length', 2),
+                            mode=native_mode, idx=0)
+                        seq.extend(new)
+                        decoding_kwargs['dls'].extend(dls_)
+                        decoding_kwargs['edls'].extend(edls_)
+                        decoding_kwargs['fts'].extend(fts_)
+                        decoding_kwargs['qts'].extend(qts_)
+                        assert fin
                         self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=0)
-                    flushed = True
-                    break
-                if native_loop:
-                    # every remaining step runs in la_lookahead_decode: same calls in the same order (hier_get -> la_llama_step
-                    # -> stream_put -> stop checks), without the interpreter between them
-                    new, dls_, edls_, fts_, qts_, fin = eng.decode_native(
-                        self.lookahead_cache, seq, stop_max_length, eos_ids=eos_set, decoding_length=decoding_length,
-                        branch_length=branch_length, max_query_length=decoding_kwargs.get('max_query_length', 2),
-                        mode=native_mode, idx=0)
-                    seq.extend(new)
-                    decoding_kwargs['dls'].extend(dls_)
-                    decoding_kwargs['edls'].extend(edls_)
-                    decoding_kwargs['fts'].extend(fts_)
-                    decoding_kwargs['qts'].extend(qts_)
-                    assert fin
-                    self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=0)
-                    flushed = True
-                    break
+                        flushed = True
+                        break
         finally:
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(1.0)              # also after an exception: the next request starts without the stage
-            if dev_sample is not None:
-                eng.set_sampling(False)
             # an exception mid-generation must not leave this request's stream buffer / input frequencies behind (they would
             # mix into the next request); the reference flushes on the normal path only (pretrained_model.py:1236-1239)
             if not flushed:
@@ -464,29 +357,15 @@ class LookaheadPreTrainedModel(object):
         eng = self.engine
         eng.reset()
         host_pick = do_sample or (logits_processor is not None and len(logits_processor) > 0)
-        dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample, enabled=device_processors) if host_pick else None
-        dev_sample = device_sampling(logits_processor, eng, do_sample=do_sample, seed=sample_seed, enabled=device_processors) if host_pick else None
-        if dev_sample is not None:
-            dev_penalty = dev_sample['penalty']
-        if dev_penalty is not None or dev_sample is not None:
+        stages = plan_device_stages(logits_processor, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
+        if stages is not None:
             host_pick = False
         custom_stop = _custom_stop(stopping_criteria)        # the caller's criteria besides the length bound, once per token
 
         def pick(row):
-            ctx = torch.tensor([seq], dtype=torch.long, device=eng.device)
-            scores = eng.logits()[row][None].clone()
-            if logits_processor is not None and len(logits_processor) > 0:
-                scores = logits_processor(ctx, scores)
-            if do_sample:
-                return int(torch.multinomial(torch.softmax(scores.float(), dim=-1), num_samples=1)[0, 0])
-            return int(torch.argmax(scores, dim=-1)[0])
+            return pick_token(logits_processor, do_sample, seq, eng.logits()[row], eng.device)[0]
 
-        try:
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(dev_penalty)
-            if dev_sample is not None:
-                eng.sampling_stream(0, 0)
-                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
+        with device_stages(eng, stages, [(0, 0, None)]):
             tok = eng.prefill(seq, fast=False) if host_pick else eng.prefill(seq)
             if host_pick:
                 tok = pick((len(seq) - 1) % 64)
@@ -500,21 +379,9 @@ class LookaheadPreTrainedModel(object):
                     toks, _ = eng.step(np.asarray([tok], dtype=np.int32), _ONE, mode=0)
                     tok = toks[0]
                 seq.append(tok)
-        finally:
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(1.0)
-            if dev_sample is not None:
-                eng.set_sampling(False)
         return torch.tensor([seq], dtype=torch.long, device=input_ids.device)
 
     # ------------------------------------------------------------------------------------------- front door
-    def _get_generation_mode(self, decoding_kwargs):
-        """pretrained_model.py:55-106 reduced to the two modes this path serves."""
-        dk = decoding_kwargs or {}
-        if dk.get('use_lookahead', False) and dk.get('decoding_length', 64) > 1 and dk.get('branch_length', 12) > 0:
-            return GenerationMode.LOOKAHEAD_GENERATION
-        return GenerationMode.GREEDY_SEARCH
-
     def generate(self, inputs=None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  prefix_allowed_tokens_fn=None, synced_gpus=None, assistant_model=None, streamer=None, **kwargs):
         """generate() with the reference's signature (common/pretrained_model.py:110-121) for the two modes this package serves —
@@ -526,39 +393,8 @@ class LookaheadPreTrainedModel(object):
         :428-441; temperature / top_k / top_p act in the sampling mode (`do_sample` without lookahead, :465-479).
         Call shapes of the reference's own callers work unchanged: examples/llama_example.py:51-60,
         benchmarks/benchmark.py:282-300."""
-        if prefix_allowed_tokens_fn is not None or assistant_model is not None:
-            raise NotImplementedError('prefix_allowed_tokens_fn / assistant_model: outside the lookahead path (SURVEY section 2, out of scope)')
-        input_ids = inputs if inputs is not None else kwargs.pop('input_ids', None)
-        kwargs.pop('input_ids', None)
-        if input_ids is None:
-            raise ValueError('generate() needs input_ids')
-        ga, model_kwargs = resolve_generate_args(self.generation_config, input_ids.size(1), generation_config=generation_config,
-                                                 logits_processor=logits_processor, stopping_criteria=stopping_criteria,
-                                                 device=getattr(getattr(self, 'engine', None), 'device', None), **kwargs)
-        attention_mask = model_kwargs.pop('attention_mask', None)
-        dk = ga.decoding_kwargs
-        if streamer is not None:
-            pass                                             # the loops feed the streamer themselves (prompt first, :318-319)
-        if self._get_generation_mode(dk) == GenerationMode.LOOKAHEAD_GENERATION:
-            dk['generation_mode'] = GenerationMode.LOOKAHEAD_GENERATION
-            dk['do_sample'] = ga.do_sample
-            la_procs = ga.logits_processor
-            if ga.do_sample and 'sample_seed' in dk:         # opt-in: the config-derived warpers reach the lookahead branch too
-                from transformers import LogitsProcessorList
-                la_procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
-            return self.lookahead_generation(input_ids, logits_processor=la_procs if len(la_procs) else None,
-                                             stopping_criteria=ga.stopping_criteria, pad_token_id=ga.pad_token_id,
-                                             eos_token_id=ga.eos_token_id, output_scores=ga.output_scores or None,
-                                             return_dict_in_generate=ga.return_dict_in_generate,
-                                             streamer=streamer, attention_mask=attention_mask, decoding_kwargs=dk)
-        from transformers import LogitsProcessorList
-        procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
-        out = self.greedy_search(input_ids, ga.max_length, ga.eos_token_id if ga.eos_token_id is not None
-                                 else getattr(self.generation_config, 'eos_token_id', None),
-                                 logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
-                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True),
-                                 sample_seed=dk.get('sample_seed', None))
-        return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out
+        return run_generate(self, False, inputs, generation_config, logits_processor, stopping_criteria, prefix_allowed_tokens_fn,
+                            assistant_model, streamer, kwargs)
 
     def stream_generate(self, *args, **kwargs):
         """pretrained_model.py:1323-1350: run generate() on a worker thread, yield from the streamer."""

@@ -15,16 +15,13 @@ gets a 64-row block of its own and the blocks of a step run in ONE pass over the
 rows through the LDS-staged GEMM family).  Tokens are unaffected by the budget (lookahead is lossless); dls/edls differ.
 """
 import time
-import warnings
 
 import numpy as np
 import torch
 
 from . import _lib
-from .lookahead_cache import LookaheadCache
-from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, device_repetition_penalty, device_sampling,
-                                          resolve_generate_args)
-from .pretrained_model import _custom_stop, _max_length_of
+from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, _custom_stop, _parents_of, begin_request, device_stages,
+                                          gc_paused, pick_token, plan_device_stages, run_generate)
 
 _ONE = np.array([1], dtype=np.uint64)
 
@@ -105,22 +102,16 @@ class LookaheadPreTrainedModel(object):
 
     @torch.no_grad()
     def lookahead_generation(self, *args, **kwargs):
-        """Entry point (signature of the reference's lookahead_generation, see _lookahead_generation).  The step loop
-        runs with the cyclic garbage collector paused: a generation-2 pass over torch's object graph stalls the host
-        thread for tens of ms (measured 37 ms = 9 verify steps) and the loop creates no reference cycles."""
-        import gc
-        was_enabled = gc.isenabled()
-        gc.disable()
-        try:
-            return self._lookahead_generation(*args, **kwargs)
-        except BaseException:
-            # an abnormal exit (KeyboardInterrupt, a raising StoppingCriteria, a failed assert) may leave device-side trie inserts
-            # the host never replayed: drop the mirror owner, the next generation builds a fresh image from the host trie
-            self._dev_trie = None
-            raise
-        finally:
-            if was_enabled:
-                gc.enable()
+        """Entry point (signature of the reference's lookahead_generation, see _lookahead_generation); the step loop runs with
+        the cyclic garbage collector paused (gc_paused)."""
+        with gc_paused():
+            try:
+                return self._lookahead_generation(*args, **kwargs)
+            except BaseException:
+                # an abnormal exit (KeyboardInterrupt, a raising StoppingCriteria, a failed assert) may leave device-side trie inserts
+                # the host never replayed: drop the mirror owner, the next generation builds a fresh image from the host trie
+                self._dev_trie = None
+                raise
 
     def _lookahead_generation(self, input_ids, logits_processor=None, stopping_criteria=None, max_length=None,
                              pad_token_id=None, eos_token_id=None, output_attentions=None,
@@ -130,38 +121,16 @@ class LookaheadPreTrainedModel(object):
         # input_ids[b, :cur+i+2] (pretrained_model_batch.py:814-875).  With an empty list and greedy decoding that walk equals the
         # device accept scan; a non-empty list or sampling takes the sequential path: forward-only step (mode 2), host walk over
         # the logits rows, host-decided commit (la_llama_bcommit / la_llama_mcommit).
-        if isinstance(logits_processor, (list, tuple)) and not callable(logits_processor):
-            from transformers import LogitsProcessorList      # a plain list of processors: the reference's generate() wraps it the same way
-            logits_processor = LogitsProcessorList(list(logits_processor))
-        sequential = (logits_processor is not None and len(logits_processor) > 0) or \
-            bool(model_kwargs.get('decoding_kwargs', {}).get('do_sample', False))
-        if output_attentions or output_hidden_states:
-            raise NotImplementedError('attentions / hidden_states are intermediates the device path never materialises '
-                                      '(fused attention, activations in MFMA fragment order); scores are returned (output_scores)')
-        gc = self.generation_config
-        pad_token_id = pad_token_id if pad_token_id is not None else getattr(gc, 'pad_token_id', None)
-        eos_token_id = eos_token_id if eos_token_id is not None else getattr(gc, 'eos_token_id', None)
-        if isinstance(eos_token_id, int):
-            eos_token_id = [eos_token_id]
-        return_dict_in_generate = bool(return_dict_in_generate) if return_dict_in_generate is not None \
-            else bool(getattr(gc, 'return_dict_in_generate', False))
-        output_scores = bool(output_scores) if output_scores is not None else bool(getattr(gc, 'output_scores', False))
         # `scores` as the reference's batch loop returns them (pretrained_model_batch.py:1145, 1247, 1263-1264): one [bs, vocab] entry per
         # loop iteration, and every entry is model_kwargs['next_tokens_scores'] — written by the PREFILL branch only (:789, :807), so the
         # tuple repeats the processed logits of the last prompt rows (pinned on tests/golden/llama_tiny_scores_fp32.npz)
-        scores = () if (return_dict_in_generate and output_scores) else None
+        logits_processor, sequential, pad_token_id, eos_token_id, return_dict_in_generate, scores, decoding_kwargs, stop_max_length = \
+            begin_request(self, logits_processor, stopping_criteria, max_length, pad_token_id, eos_token_id, output_attentions,
+                          output_hidden_states, output_scores, return_dict_in_generate, model_kwargs)
         prefill_scores = None
-        if not hasattr(self, 'lookahead_cache') or self.lookahead_cache is None:
-            self.lookahead_cache = LookaheadCache()
-        decoding_kwargs = model_kwargs['decoding_kwargs']
-        self.lookahead_cache.eos_ids = eos_token_id
-        self.lookahead_cache.stop_words = decoding_kwargs.get('stop_words', {})
         pad = pad_token_id if pad_token_id is not None else 2
-        decoding_kwargs.update({'pad': pad, 'edls': [], 'dls': [], 'fts': [], 'qts': []})
+        decoding_kwargs['pad'] = pad
         decoding_kwargs['_n_samples'] = int(input_ids.shape[0])
-        stop_max_length = _max_length_of(stopping_criteria, max_length)
-        if stop_max_length is None:
-            raise ValueError('lookahead_generation needs a MaxLengthCriteria (stopping_criteria.max_length)')
         custom_stop = _custom_stop(stopping_criteria)
         decoding_length = decoding_kwargs.get('decoding_length', 63)
         decoding_kwargs['max_length'] = stop_max_length
@@ -222,22 +191,14 @@ class LookaheadPreTrainedModel(object):
         # input_ids[b, :cur + i + 2], left pads included, so every slot's context set is seeded with its PADDED row.  Other lists,
         # sampling, scores, requests in which a sample's tree may be wider than one block, the device trie and sharded jobs keep
         # the host walk.
-        dev_penalty = None
-        if sequential and scores is None and gather is None and not decoding_kwargs.get('device_trie', False) and \
-                min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX:
-            dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=bool(decoding_kwargs.get('do_sample', False)),
-                                                    enabled=decoding_kwargs.get('device_processors', True))
         # a do_sample request with decoding_kwargs['sample_seed'] and a list device_sampling accepts: the sampling stage of the
         # device step (csrc/la_sample.hip) under the same conditions, stream word of a slot = its batch index
-        dev_sample = None
-        if sequential and scores is None and gather is None and not decoding_kwargs.get('device_trie', False) and \
-                min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX:
-            dev_sample = device_sampling(logits_processor, eng, do_sample=bool(decoding_kwargs.get('do_sample', False)),
-                                         seed=decoding_kwargs.get('sample_seed', None),
-                                         enabled=decoding_kwargs.get('device_processors', True))
-        if dev_sample is not None:
-            dev_penalty = dev_sample['penalty']
-        if dev_penalty is not None or dev_sample is not None:
+        do_sample = bool(decoding_kwargs.get('do_sample', False))
+        stages = plan_device_stages(logits_processor, eng, sequential and scores is None and gather is None
+                                    and not decoding_kwargs.get('device_trie', False)
+                                    and min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX, do_sample=do_sample,
+                                    seed=decoding_kwargs.get('sample_seed', None), enabled=decoding_kwargs.get('device_processors', True))
+        if stages is not None:
             sequential = False
             decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the penalty / sampling stage)
         finished_rows = [None] * bs
@@ -246,238 +207,222 @@ class LookaheadPreTrainedModel(object):
         try:
             ts = time.time()
             eng.reset_slot(-1)
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(dev_penalty)
-                for i in range(bs):
-                    eng.seed_penalty_context(i, ids0[i].tolist())
-            if dev_sample is not None:
-                for i in range(bs):
-                    eng.sampling_stream(i, i)
-                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
-            # prefill: valid prompt tokens of every sample, packed into shared 64-row chain blocks
-            prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
-            multi = bool(getattr(eng, 'max_blocks', 0))
-            do_sample = bool(decoding_kwargs.get('do_sample', False))
+            with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)]):      # (stream word = batch index, seed = padded row)
+                # prefill: valid prompt tokens of every sample, packed into shared 64-row chain blocks
+                prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
+                multi = bool(getattr(eng, 'max_blocks', 0))
+                picked = [None]
 
-            picked = [None]
+                def pick(ctx_ids, row):
+                    tok, picked[0] = pick_token(logits_processor, do_sample, ctx_ids, row, eng.device)
+                    return tok
 
-            def pick(ctx_ids, row):
-                """next token from one logits row through the processor list (pretrained_model_batch.py:840-846)"""
-                sc = row[None]
-                if logits_processor is not None and len(logits_processor) > 0:
-                    ctx = torch.tensor([ctx_ids], dtype=torch.long, device=eng.device)
-                    sc = logits_processor(ctx, sc.clone())
-                picked[0] = sc
-                if do_sample:
-                    return int(torch.multinomial(torch.softmax(sc.float(), dim=-1), num_samples=1)[0, 0])
-                return int(torch.argmax(sc, dim=-1)[0])
-
-            if sequential or scores is not None:
-                # prompts one slot after the other: the last prompt row's logits stay readable for the processor call of :783
-                # (batch-wise there; the processors are row-wise, so one padded row at a time is the same call)
-                first, rows_sc = {}, []
-                for i in range(bs):
-                    n = len(prompts[i])
-                    if multi:
-                        tok = eng.mprefill(i, prompts[i])
-                        last = (n - 1) % (64 * eng.max_blocks)
-                        t = pick(ids0[i].tolist(), eng.mlogits()[last])
-                    else:
-                        tok = eng.bprefill(i, prompts[i])
-                        t = pick(ids0[i].tolist(), eng.logits()[(n - 1) % 64])
-                    first[i] = t if sequential else tok
-                    rows_sc.append(picked[0].clone())
-                if scores is not None:
-                    prefill_scores = torch.cat(rows_sc, 0).to(out_device)
-            else:
-                first = eng.mprefill_many(prompts) if multi else eng.bprefill_many(prompts)
-            next_token_list = [[first[i]] for i in range(bs)]
-            dmode = decoding_kwargs.get('decoding_mode', 'hier')
-            # decoding_kwargs['device_trie']: True / False, or absent = AUTO (round 6): the on-GPU trie chained in front of the verify pass
-            # from 8 sequences per GPU on, where one launch of the workgroup-per-query kernel (~120 us whatever the batch) beats the
-            # host's per-sample queries + input upload (Mistral-7B bs=8: 9.58 vs 9.62 ms per step, profiles/r06_device_trie_wg.txt)
-            chain_ok = multi and not sequential and streamer is None and \
-                bool(decoding_kwargs.get('per_sample_budget', False)) and dmode.split('_')[0] in ('hier', 'one') and \
-                int(decoding_length) <= _lib.LA_TREE_MAX and \
-                not decoding_kwargs.get('debug_lookahead', False)
-            if decoding_kwargs.get('device_trie', None) is None:
-                decoding_kwargs['device_trie'] = bool(chain_ok and bs >= 8 and gather is None and dmode.split('_')[0] == 'hier')
-            chained = bool(decoding_kwargs['device_trie']) and chain_ok
-            # device_trie_update (default on with the chained device trie): the trie UPDATE of every step runs on the device as well
-            dev_put = chained and bool(decoding_kwargs.get('device_trie_update', True)) and branch_length + 1 <= 64
-            put_on_device, buffers_loaded = False, False
-            replay_due, full_image_due, replay_calls = None, False, 1      # puts of the last chained step the host trie has not repeated yet
-            decoding_kwargs['dls'].extend([1] * bs)
-            decoding_kwargs['edls'].extend([1] * bs)
-            max_cur = 0
-            while True:
-                for k, b in enumerate(batch_indices):
-                    rows[b].extend(next_token_list[k])
-                if streamer is not None:
-                    streamer.put(np.array(next_token_list[0]))
-                if put_on_device:
-                    # the device inserted these tokens into its trie image itself, straight from the step's output block
-                    # (la_trie_stream_put_dev behind the verify pass): the host trie repeats the same puts in the same order and
-                    # drops the words it logged for them — nothing of the update crosses PCIe.  Round 4: the replay is deferred until
-                    # the NEXT step's kernels are queued (the device image needs nothing from the host), so it overlaps the GPU step
-                    replay_due = [(b, next_token_list[k]) for k, b in enumerate(batch_indices)]
-                    put_on_device = False
-                elif gather is None:                                                # :1254-1259, one native call for the batch
-                    puts = [(b, [x for x in next_token_list[k] if x != -1]) for k, b in enumerate(batch_indices)]
-                    if overlap_put:
-                        run_deferred_put()                                          # (a step that found no overlap point)
-                        deferred_put[0] = puts
-                    else:
-                        self.lookahead_cache.stream_put_many(puts, branch_length=branch_length + 1, final=False)
-                max_cur = max(max_cur, max(len(rows[b]) - 1 for b in batch_indices))
-                keep = []
-                for k, b in enumerate(batch_indices):                               # :1269-1276 + _early_stop :937-980
-                    if len(rows[b]) >= stop_max_length or any(t in eos_set for t in next_token_list[k]) or \
-                            (custom_stop is not None and custom_stop(rows[b], out_device, scores)):        # :1284
-                        finished_rows[b] = list(rows[b])
-                    else:
-                        keep.append(b)
-                if gather is not None:
-                    # one collective per loop iteration on every rank: this rank's lists in local row order ([] for retired rows), DONE once
-                    # no row is left; strict = gathered and applied now, split-phase = applied under the next verify pass (overlap below)
-                    mine = [[] for _ in range(bs)]
-                    for k, b in enumerate(batch_indices):
-                        mine[b] = [x for x in next_token_list[k] if x != -1]
-                    gather.step_update(self.lookahead_cache, mine, branch_length, done=not keep)
-                batch_indices = keep
-                if scores is not None:
-                    scores += (prefill_scores,)
-                te = time.time()
-                decoding_kwargs['fts'].append(te - ts)
-                ts = te
-                if not batch_indices:
-                    break
-                if chained:
-                    dt0 = self._device_trie(decoding_kwargs['_n_samples'], dev_put, narrow=True)
-                    if replay_due is not None and (len(batch_indices) > eng.max_blocks or full_image_due):
-                        # several engine passes per step, or the host image outgrew the device's: replay first, then a synced query
-                        dt0.replay(replay_due, branch_length + 1, calls=replay_calls)
-                        replay_due, full_image_due = None, False
-                    # device trie chained in front of the verify pass (la_llama_mstep_trie): ONE query launch for all active samples on the
-                    # engine's stream, the step input assembled on the device from its outputs, one 64-row block per sample — no draft
-                    # crosses PCIe in either direction; the host reads back the accepted tokens and the draft lengths only.  Same budget
-                    # rule as the host path with per_sample_budget (lookahead_cache.py:534-541).
-                    ts_q = time.time()
-                    qids = [rows[b][-2:] for b in batch_indices]
-                    per = min(decoding_length, _lib.LA_TREE_MAX)
-                    dm = decoding_kwargs.get('decoding_mode', 'hier')
-                    mode_q = (dm if '_' in dm else dm + '_mix').split('_')[1]
-                    dt = self._device_trie(decoding_kwargs['_n_samples'], dev_put, narrow=True)
-                    with torch.cuda.stream(eng.stream):
-                        if dm.split('_')[0] == 'one':
-                            dt.one_get_dev(qids, idxs=batch_indices, decoding_length=per, branch_length=branch_length, mode=mode_q,
-                                           sync=replay_due is None)
+                if sequential or scores is not None:
+                    # prompts one slot after the other: the last prompt row's logits stay readable for the processor call of :783
+                    # (batch-wise there; the processors are row-wise, so one padded row at a time is the same call)
+                    first, rows_sc = {}, []
+                    for i in range(bs):
+                        n = len(prompts[i])
+                        if multi:
+                            tok = eng.mprefill(i, prompts[i])
+                            last = (n - 1) % (64 * eng.max_blocks)
+                            t = pick(ids0[i].tolist(), eng.mlogits()[last])
                         else:
-                            dt.hier_get_dev(qids, idxs=batch_indices, decoding_length=per, branch_length=branch_length, min_input_size=0,
-                                            min_output_size=max(per // 2, 1), mode=mode_q, sync=replay_due is None)
-                        if dev_put and not buffers_loaded:
-                            dt.load_stream_buffers()        # the hold-back buffers as the host's stream_put calls left them
-                            buffers_loaded = True
-                        emitted, widths = {}, []
-                        for g0 in range(0, len(batch_indices), eng.max_blocks):
-                            grp = batch_indices[g0:g0 + eng.max_blocks]
-                            eng.mstep_trie_async(dt, g0, grp, [stop_max_length - (len(rows[b]) - 1) - 1 for b in grp],
-                                                 [rows[b][-1] for b in grp], put_idxs=grp if dev_put else None,
-                                                 put_branch_length=branch_length + 1)
-                            if replay_due is not None:         # the previous step's update, on the host trie, while the GPU verifies
-                                full_image_due = not dt.replay(replay_due, branch_length + 1, calls=replay_calls)
-                                replay_due = None
-                            toks, Ts = eng.mstep_trie_finish()
-                            for b, tk in zip(grp, toks):
-                                emitted[b] = tk
-                            widths.extend(Ts)
-                        put_on_device = dev_put
-                        replay_calls = (len(batch_indices) + eng.max_blocks - 1) // eng.max_blocks       # stream_put_dev calls of this step
-                    decoding_kwargs['qts'].append(time.time() - ts_q)
-                    decoding_kwargs.update({'decoding_qids': qids, 'decoding_ids': None, 'hit_sizes': None, 'batch_indices': batch_indices})
-                    width = max(widths)
+                            tok = eng.bprefill(i, prompts[i])
+                            t = pick(ids0[i].tolist(), eng.logits()[(n - 1) % 64])
+                        first[i] = t if sequential else tok
+                        rows_sc.append(picked[0].clone())
+                    if scores is not None:
+                        prefill_scores = torch.cat(rows_sc, 0).to(out_device)
+                else:
+                    first = eng.mprefill_many(prompts) if multi else eng.bprefill_many(prompts)
+                next_token_list = [[first[i]] for i in range(bs)]
+                dmode = decoding_kwargs.get('decoding_mode', 'hier')
+                # decoding_kwargs['device_trie']: True / False, or absent = AUTO (round 6): the on-GPU trie chained in front of the verify pass
+                # from 8 sequences per GPU on, where one launch of the workgroup-per-query kernel (~120 us whatever the batch) beats the
+                # host's per-sample queries + input upload (Mistral-7B bs=8: 9.58 vs 9.62 ms per step, profiles/r06_device_trie_wg.txt)
+                chain_ok = multi and not sequential and streamer is None and \
+                    bool(decoding_kwargs.get('per_sample_budget', False)) and dmode.split('_')[0] in ('hier', 'one') and \
+                    int(decoding_length) <= _lib.LA_TREE_MAX and \
+                    not decoding_kwargs.get('debug_lookahead', False)
+                if decoding_kwargs.get('device_trie', None) is None:
+                    decoding_kwargs['device_trie'] = bool(chain_ok and bs >= 8 and gather is None and dmode.split('_')[0] == 'hier')
+                chained = bool(decoding_kwargs['device_trie']) and chain_ok
+                # device_trie_update (default on with the chained device trie): the trie UPDATE of every step runs on the device as well
+                dev_put = chained and bool(decoding_kwargs.get('device_trie_update', True)) and branch_length + 1 <= 64
+                put_on_device, buffers_loaded = False, False
+                replay_due, full_image_due, replay_calls = None, False, 1      # puts of the last chained step the host trie has not repeated yet
+                decoding_kwargs['dls'].extend([1] * bs)
+                decoding_kwargs['edls'].extend([1] * bs)
+                max_cur = 0
+                while True:
+                    for k, b in enumerate(batch_indices):
+                        rows[b].extend(next_token_list[k])
+                    if streamer is not None:
+                        streamer.put(np.array(next_token_list[0]))
+                    if put_on_device:
+                        # the device inserted these tokens into its trie image itself, straight from the step's output block
+                        # (la_trie_stream_put_dev behind the verify pass): the host trie repeats the same puts in the same order and
+                        # drops the words it logged for them — nothing of the update crosses PCIe.  Round 4: the replay is deferred until
+                        # the NEXT step's kernels are queued (the device image needs nothing from the host), so it overlaps the GPU step
+                        replay_due = [(b, next_token_list[k]) for k, b in enumerate(batch_indices)]
+                        put_on_device = False
+                    elif gather is None:                                                # :1254-1259, one native call for the batch
+                        puts = [(b, [x for x in next_token_list[k] if x != -1]) for k, b in enumerate(batch_indices)]
+                        if overlap_put:
+                            run_deferred_put()                                          # (a step that found no overlap point)
+                            deferred_put[0] = puts
+                        else:
+                            self.lookahead_cache.stream_put_many(puts, branch_length=branch_length + 1, final=False)
+                    max_cur = max(max_cur, max(len(rows[b]) - 1 for b in batch_indices))
+                    keep = []
+                    for k, b in enumerate(batch_indices):                               # :1269-1276 + _early_stop :937-980
+                        if len(rows[b]) >= stop_max_length or any(t in eos_set for t in next_token_list[k]) or \
+                                (custom_stop is not None and custom_stop(rows[b], out_device, scores)):        # :1284
+                            finished_rows[b] = list(rows[b])
+                        else:
+                            keep.append(b)
+                    if gather is not None:
+                        # one collective per loop iteration on every rank: this rank's lists in local row order ([] for retired rows), DONE once
+                        # no row is left; strict = gathered and applied now, split-phase = applied under the next verify pass (overlap below)
+                        mine = [[] for _ in range(bs)]
+                        for k, b in enumerate(batch_indices):
+                            mine[b] = [x for x in next_token_list[k] if x != -1]
+                        gather.step_update(self.lookahead_cache, mine, branch_length, done=not keep)
+                    batch_indices = keep
+                    if scores is not None:
+                        scores += (prefill_scores,)
+                    te = time.time()
+                    decoding_kwargs['fts'].append(te - ts)
+                    ts = te
+                    if not batch_indices:
+                        break
+                    if chained:
+                        dt0 = self._device_trie(decoding_kwargs['_n_samples'], dev_put, narrow=True)
+                        if replay_due is not None and (len(batch_indices) > eng.max_blocks or full_image_due):
+                            # several engine passes per step, or the host image outgrew the device's: replay first, then a synced query
+                            dt0.replay(replay_due, branch_length + 1, calls=replay_calls)
+                            replay_due, full_image_due = None, False
+                        # device trie chained in front of the verify pass (la_llama_mstep_trie): ONE query launch for all active samples on the
+                        # engine's stream, the step input assembled on the device from its outputs, one 64-row block per sample — no draft
+                        # crosses PCIe in either direction; the host reads back the accepted tokens and the draft lengths only.  Same budget
+                        # rule as the host path with per_sample_budget (lookahead_cache.py:534-541).
+                        ts_q = time.time()
+                        qids = [rows[b][-2:] for b in batch_indices]
+                        per = min(decoding_length, _lib.LA_TREE_MAX)
+                        dm = decoding_kwargs.get('decoding_mode', 'hier')
+                        mode_q = (dm if '_' in dm else dm + '_mix').split('_')[1]
+                        dt = self._device_trie(decoding_kwargs['_n_samples'], dev_put, narrow=True)
+                        with torch.cuda.stream(eng.stream):
+                            if dm.split('_')[0] == 'one':
+                                dt.one_get_dev(qids, idxs=batch_indices, decoding_length=per, branch_length=branch_length, mode=mode_q,
+                                               sync=replay_due is None)
+                            else:
+                                dt.hier_get_dev(qids, idxs=batch_indices, decoding_length=per, branch_length=branch_length, min_input_size=0,
+                                                min_output_size=max(per // 2, 1), mode=mode_q, sync=replay_due is None)
+                            if dev_put and not buffers_loaded:
+                                dt.load_stream_buffers()        # the hold-back buffers as the host's stream_put calls left them
+                                buffers_loaded = True
+                            emitted, widths = {}, []
+                            for g0 in range(0, len(batch_indices), eng.max_blocks):
+                                grp = batch_indices[g0:g0 + eng.max_blocks]
+                                eng.mstep_trie_async(dt, g0, grp, [stop_max_length - (len(rows[b]) - 1) - 1 for b in grp],
+                                                     [rows[b][-1] for b in grp], put_idxs=grp if dev_put else None,
+                                                     put_branch_length=branch_length + 1)
+                                if replay_due is not None:         # the previous step's update, on the host trie, while the GPU verifies
+                                    full_image_due = not dt.replay(replay_due, branch_length + 1, calls=replay_calls)
+                                    replay_due = None
+                                toks, Ts = eng.mstep_trie_finish()
+                                for b, tk in zip(grp, toks):
+                                    emitted[b] = tk
+                                widths.extend(Ts)
+                            put_on_device = dev_put
+                            replay_calls = (len(batch_indices) + eng.max_blocks - 1) // eng.max_blocks       # stream_put_dev calls of this step
+                        decoding_kwargs['qts'].append(time.time() - ts_q)
+                        decoding_kwargs.update({'decoding_qids': qids, 'decoding_ids': None, 'hit_sizes': None, 'batch_indices': batch_indices})
+                        width = max(widths)
+                        next_token_list = [emitted[b] for b in batch_indices]
+                        for k in range(len(batch_indices)):
+                            decoding_kwargs['dls'].append(width)
+                            decoding_kwargs['edls'].append(len(next_token_list[k]))
+                        continue
+                    drafts = self.lookahead_prepare_inputs_for_generation([rows[b] for b in batch_indices], [gi(b) for b in batch_indices],
+                                                                          decoding_kwargs)
+                    segments = []
+                    for b, (d_ids, d_rm) in zip(batch_indices, drafts):
+                        if len(d_ids) == 0:
+                            d_ids, d_rm = np.asarray(rows[b][-1:], dtype=np.int32), _ONE
+                        cur = len(rows[b]) - 1
+                        segments.append((b, d_ids, d_rm, 2 if sequential else 0, stop_max_length - cur - 1))
+                    if sum(len(sg[1]) for sg in segments) <= _lib.LA_TREE_MAX and all(np.ndim(sg[2]) == 1 for sg in segments):
+                        run_deferred_put()                                     # (bstep has no asynchronous form: same order, no overlap)
+                        if gather is not None:
+                            gather.overlap(self.lookahead_cache, branch_length)
+                        emitted = eng.bstep(segments)                          # the whole batch shares one 64-row block
+                        if sequential:
+                            base, logits = eng.bstep_rows(), eng.logits()
+                            kept = {}
+                            for sg in segments:
+                                emitted[sg[0]], kept[sg[0]] = self._sequential_walk(rows[sg[0]], sg, logits, base[sg[0]], pick)
+                            eng.bcommit(kept)
+                    else:
+                        assert multi, 'more than 64 draft rows per step need an engine created with max_blocks > 1'
+                        emitted = {}
+                        # ceil(T / 64) blocks per sample (1 for the usual 64-row trees), as many samples per pass as max_blocks holds
+                        groups, cur_g, cur_b = [], [], 0
+                        for sg in segments:
+                            nb_ = (len(sg[1]) + 63) // 64
+                            assert nb_ <= eng.max_blocks, f'a {len(sg[1])}-row tree needs an engine created with max_blocks >= {nb_}'
+                            if cur_b + nb_ > eng.max_blocks:
+                                groups.append(cur_g)
+                                cur_g, cur_b = [], 0
+                            cur_g.append(sg)
+                            cur_b += nb_
+                        groups.append(cur_g)
+                        for group in groups:
+                            wide_pass = any(len(sg[1]) > 64 or np.ndim(sg[2]) == 2 for sg in group)
+                            if wide_pass or not hasattr(eng, 'mstep_async'):
+                                run_deferred_put()
+                                if gather is not None:
+                                    gather.overlap(self.lookahead_cache, branch_length)
+                                out = eng.mstep_trees(group) if wide_pass else eng.mstep(group)
+                            else:
+                                # queue the pass, then do the host work nothing on the device waits for — the deferred trie update / the
+                                # previous step's gather and its puts — while the GPU verifies
+                                eng.mstep_async(group)
+                                run_deferred_put()
+                                if gather is not None:
+                                    gather.overlap(self.lookahead_cache, branch_length)
+                                out = eng.mstep_finish()
+                            if sequential:
+                                logits, kept, base = eng.mlogits(), [], 0
+                                for sg in group:
+                                    toks, keep_rows = self._sequential_walk(rows[sg[0]], sg, logits, base, pick)
+                                    emitted[sg[0]] = toks
+                                    kept.append(keep_rows)
+                                    base += 64 * ((len(sg[1]) + 63) // 64)
+                                if wide_pass:
+                                    eng.mcommit_trees(kept, [len(sg[1]) for sg in group])
+                                else:
+                                    eng.mcommit(kept)
+                                continue
+                            for sg, toks in zip(group, out):
+                                emitted[sg[0]] = toks
+                    width = max(len(sg[1]) for sg in segments)
                     next_token_list = [emitted[b] for b in batch_indices]
                     for k in range(len(batch_indices)):
                         decoding_kwargs['dls'].append(width)
                         decoding_kwargs['edls'].append(len(next_token_list[k]))
-                    continue
-                drafts = self.lookahead_prepare_inputs_for_generation([rows[b] for b in batch_indices], [gi(b) for b in batch_indices],
-                                                                      decoding_kwargs)
-                segments = []
-                for b, (d_ids, d_rm) in zip(batch_indices, drafts):
-                    if len(d_ids) == 0:
-                        d_ids, d_rm = np.asarray(rows[b][-1:], dtype=np.int32), _ONE
-                    cur = len(rows[b]) - 1
-                    segments.append((b, d_ids, d_rm, 2 if sequential else 0, stop_max_length - cur - 1))
-                if sum(len(sg[1]) for sg in segments) <= _lib.LA_TREE_MAX and all(np.ndim(sg[2]) == 1 for sg in segments):
-                    run_deferred_put()                                     # (bstep has no asynchronous form: same order, no overlap)
-                    if gather is not None:
-                        gather.overlap(self.lookahead_cache, branch_length)
-                    emitted = eng.bstep(segments)                          # the whole batch shares one 64-row block
-                    if sequential:
-                        base, logits = eng.bstep_rows(), eng.logits()
-                        kept = {}
-                        for sg in segments:
-                            emitted[sg[0]], kept[sg[0]] = self._sequential_walk(rows[sg[0]], sg, logits, base[sg[0]], pick)
-                        eng.bcommit(kept)
+                if replay_due is not None:                                              # the last step's update (the loop ended before another launch)
+                    self._device_trie(decoding_kwargs['_n_samples'], dev_put, narrow=True).replay(replay_due, branch_length + 1, calls=replay_calls)
+                    replay_due = None
+                run_deferred_put()
+                if gather is not None:
+                    gather.drain(self.lookahead_cache, branch_length)                   # until every rank has finished its sequences
+                    gather.flush(self.lookahead_cache, branch_length)                   # :1288-1290 for all B sequences, batch-index order
                 else:
-                    assert multi, 'more than 64 draft rows per step need an engine created with max_blocks > 1'
-                    emitted = {}
-                    # ceil(T / 64) blocks per sample (1 for the usual 64-row trees), as many samples per pass as max_blocks holds
-                    groups, cur_g, cur_b = [], [], 0
-                    for sg in segments:
-                        nb_ = (len(sg[1]) + 63) // 64
-                        assert nb_ <= eng.max_blocks, f'a {len(sg[1])}-row tree needs an engine created with max_blocks >= {nb_}'
-                        if cur_b + nb_ > eng.max_blocks:
-                            groups.append(cur_g)
-                            cur_g, cur_b = [], 0
-                        cur_g.append(sg)
-                        cur_b += nb_
-                    groups.append(cur_g)
-                    for group in groups:
-                        wide_pass = any(len(sg[1]) > 64 or np.ndim(sg[2]) == 2 for sg in group)
-                        if wide_pass or not hasattr(eng, 'mstep_async'):
-                            run_deferred_put()
-                            if gather is not None:
-                                gather.overlap(self.lookahead_cache, branch_length)
-                            out = eng.mstep_trees(group) if wide_pass else eng.mstep(group)
-                        else:
-                            # queue the pass, then do the host work nothing on the device waits for — the deferred trie update / the
-                            # previous step's gather and its puts — while the GPU verifies
-                            eng.mstep_async(group)
-                            run_deferred_put()
-                            if gather is not None:
-                                gather.overlap(self.lookahead_cache, branch_length)
-                            out = eng.mstep_finish()
-                        if sequential:
-                            logits, kept, base = eng.mlogits(), [], 0
-                            for sg in group:
-                                toks, keep_rows = self._sequential_walk(rows[sg[0]], sg, logits, base, pick)
-                                emitted[sg[0]] = toks
-                                kept.append(keep_rows)
-                                base += 64 * ((len(sg[1]) + 63) // 64)
-                            if wide_pass:
-                                eng.mcommit_trees(kept, [len(sg[1]) for sg in group])
-                            else:
-                                eng.mcommit(kept)
-                            continue
-                        for sg, toks in zip(group, out):
-                            emitted[sg[0]] = toks
-                width = max(len(sg[1]) for sg in segments)
-                next_token_list = [emitted[b] for b in batch_indices]
-                for k in range(len(batch_indices)):
-                    decoding_kwargs['dls'].append(width)
-                    decoding_kwargs['edls'].append(len(next_token_list[k]))
-            if replay_due is not None:                                              # the last step's update (the loop ended before another launch)
-                self._device_trie(decoding_kwargs['_n_samples'], dev_put, narrow=True).replay(replay_due, branch_length + 1, calls=replay_calls)
-                replay_due = None
-            run_deferred_put()
-            if gather is not None:
-                gather.drain(self.lookahead_cache, branch_length)                   # until every rank has finished its sequences
-                gather.flush(self.lookahead_cache, branch_length)                   # :1288-1290 for all B sequences, batch-index order
-            else:
-                for i in range(bs):                                                 # :1288-1290
-                    self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=i)
+                    for i in range(bs):                                                 # :1288-1290
+                        self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=i)
         except BaseException:
             # A failure (or an interrupt) mid-request must not leave the trie with this request's stream buffers / input frequencies, and in a
             # sharded job must not strand the other ranks: they are (or will be) waiting in the per-step collective.  The failing rank keeps
@@ -493,11 +438,6 @@ class LookaheadPreTrainedModel(object):
                 for i in range(bs):
                     self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=i)
             raise
-        finally:
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(1.0)          # also after an exception: the next request starts without the stage
-            if dev_sample is not None:
-                eng.set_sampling(False)
         if streamer is not None:
             streamer.end()
         seqs = np.full((bs, max_cur + 1), pad, dtype=np.int64)
@@ -518,17 +458,7 @@ class LookaheadPreTrainedModel(object):
         token (first such row in DFS order).  -> (emitted tokens, kept tree rows, root first)."""
         _, d_ids, d_rm, _, limit = segment
         T = len(d_ids)
-        parent = [-1] * T
-        wide = np.ndim(d_rm) == 2
-        for j in range(1, T):
-            if wide:                                   # multi-word row mask: word w = tree columns 64 w .. 64 w + 63
-                full = 0
-                for w in range(d_rm.shape[1]):
-                    full |= int(d_rm[j][w]) << (64 * w)
-            else:
-                full = int(d_rm[j])
-            below = full & ((1 << j) - 1)
-            parent[j] = below.bit_length() - 1
+        parent = _parents_of(d_rm, T)
         limit = max(1, min(int(limit), 32))
         cur, kept, toks = 0, [0], []
         while True:
@@ -560,42 +490,21 @@ class LookaheadPreTrainedModel(object):
         prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
         host_pick = do_sample or (logits_processor is not None and len(logits_processor) > 0)
         multi = bool(getattr(eng, 'max_blocks', 0))
-        # exactly one repetition penalty: the device stage of lookahead_generation, every slot seeded with its padded row
-        dev_penalty = device_repetition_penalty(logits_processor, eng, do_sample=do_sample, enabled=device_processors) if host_pick else None
-        # a do_sample request with an int sample_seed whose list device_sampling accepts: the sampling stage (stream = batch index)
-        dev_sample = device_sampling(logits_processor, eng, do_sample=do_sample, seed=sample_seed, enabled=device_processors) if host_pick else None
-        if dev_sample is not None:
-            dev_penalty = dev_sample['penalty']
-        if dev_penalty is not None or dev_sample is not None:
+        # the device stages of lookahead_generation: exactly one repetition penalty, or a do_sample request with an int sample_seed whose
+        # list device_sampling accepts; every slot seeded with its padded row, stream word = batch index
+        stages = plan_device_stages(logits_processor, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
+        if stages is not None:
             host_pick = False
-        try:
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(dev_penalty)
-                for i in range(bs):
-                    eng.seed_penalty_context(i, ids0[i].tolist())
-            if dev_sample is not None:
-                for i in range(bs):
-                    eng.sampling_stream(i, i)
-                eng.set_sampling(True, dev_sample['seed'], dev_sample['temperature'], dev_sample['top_k'], dev_sample['top_p'])
+        with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)]):
             return self._greedy_search(eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length,
                                        eos, pad_token_id, input_ids.device)
-        finally:
-            if dev_penalty is not None:
-                eng.set_repetition_penalty(1.0)
-            if dev_sample is not None:
-                eng.set_sampling(False)
 
     def _greedy_search(self, eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length, eos,
                        pad_token_id, out_device):
         bs = ids0.shape[0]
 
         def pick(ctx_ids, row):
-            scores = row[None]
-            if logits_processor is not None and len(logits_processor) > 0:
-                scores = logits_processor(torch.tensor([ctx_ids], dtype=torch.long, device=eng.device), scores.clone())
-            if do_sample:
-                return int(torch.multinomial(torch.softmax(scores.float(), dim=-1), num_samples=1)[0, 0])
-            return int(torch.argmax(scores, dim=-1)[0])
+            return pick_token(logits_processor, do_sample, ctx_ids, row, eng.device)[0]
 
         if host_pick:
             first = {}
@@ -640,34 +549,5 @@ class LookaheadPreTrainedModel(object):
         pretrained_model.py:110-372): see LookaheadPreTrainedModel.generate of pretrained_model.py here — one resolver
         (lookahead_generation_utils.resolve_generate_args) serves both.  A non-empty processor list / do_sample take the
         sequential accept path (host-side token pick), everything else stays on the device."""
-        if prefix_allowed_tokens_fn is not None or assistant_model is not None:
-            raise NotImplementedError('prefix_allowed_tokens_fn / assistant_model: outside the lookahead path (SURVEY section 2, out of scope)')
-        input_ids = inputs if inputs is not None else kwargs.pop('input_ids', None)
-        kwargs.pop('input_ids', None)
-        if input_ids is None:
-            raise ValueError('generate() needs input_ids')
-        ga, model_kwargs = resolve_generate_args(self.generation_config, input_ids.size(1), generation_config=generation_config,
-                                                 logits_processor=logits_processor, stopping_criteria=stopping_criteria,
-                                                 device=getattr(getattr(self, 'engine', None), 'device', None), **kwargs)
-        attention_mask = model_kwargs.pop('attention_mask', None)
-        dk = ga.decoding_kwargs
-        if dk.get('use_lookahead', False) and dk.get('decoding_length', 64) > 1 and dk.get('branch_length', 12) > 0:
-            dk['do_sample'] = ga.do_sample
-            la_procs = ga.logits_processor
-            if ga.do_sample and 'sample_seed' in dk:         # opt-in: the config-derived warpers reach the lookahead branch too
-                from transformers import LogitsProcessorList
-                la_procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
-            return self.lookahead_generation(input_ids, logits_processor=la_procs if len(la_procs) else None,
-                                             stopping_criteria=ga.stopping_criteria, pad_token_id=ga.pad_token_id,
-                                             eos_token_id=ga.eos_token_id, return_dict_in_generate=ga.return_dict_in_generate,
-                                             streamer=streamer, attention_mask=attention_mask, decoding_kwargs=dk)
-        from transformers import LogitsProcessorList
-        procs = LogitsProcessorList(list(ga.logits_processor) + list(ga.logits_warper))
-        out = self.greedy_search(input_ids, ga.max_length, attention_mask=attention_mask,
-                                 eos_token_id=ga.eos_token_id if ga.eos_token_id is not None
-                                 else getattr(self.generation_config, 'eos_token_id', None),
-                                 pad_token_id=ga.pad_token_id if ga.pad_token_id is not None else 0,
-                                 logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
-                                 stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True),
-                                 sample_seed=dk.get('sample_seed', None))
-        return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out
+        return run_generate(self, True, inputs, generation_config, logits_processor, stopping_criteria, prefix_allowed_tokens_fn,
+                            assistant_model, streamer, kwargs)

@@ -644,6 +644,63 @@ def test_batch_request_with_wide_trees_keeps_the_host_walk(monkeypatch):
     assert outs[0] == outs[1]
 
 
+@pytest.mark.parametrize('stage', ['penalty', 'sampling'])
+@pytest.mark.parametrize('batch', [False, True], ids=['bs1', 'batch-of-2'])
+def test_request_that_raises_leaves_no_stage_behind(batch, stage):
+    """a request with the penalty / sampling stage on is ended by a raising StoppingCriteria after its first step (lookahead loop and
+    plain loop): the next request on the same model, with no processor, emits exactly what a fresh model emits and launches no stage"""
+    from transformers import (LogitsProcessorList, MaxLengthCriteria, RepetitionPenaltyLogitsProcessor, StoppingCriteria,
+                              StoppingCriteriaList, TemperatureLogitsWarper, TopKLogitsWarper)
+
+    class Boom(StoppingCriteria):
+        def __call__(self, input_ids, scores, **kw):
+            raise RuntimeError('boom')
+
+    shape, sd = tiny_shape(), _bf16_sd()
+    rs = np.random.RandomState(21)
+    n_new = 8
+    if batch:
+        ids_np, am_np = _padded([rs.randint(3, shape.vocab, size=n).tolist() for n in (17, 11)])
+        ids, extra = torch.from_numpy(ids_np), {'attention_mask': torch.from_numpy(am_np)}
+
+        def make():
+            return BatchLlama(shape, dict(sd), max_length=256, max_batch=2, eos_token_id=None, max_blocks=0)
+    else:
+        ids, extra = torch.tensor([rs.randint(3, shape.vocab, size=17).tolist()]), {}
+
+        def make():
+            return LlamaForCausalLM(shape, dict(sd), max_length=256, eos_token_id=None)
+    P = ids.shape[1]
+    sampling = stage == 'sampling'
+    procs = LogitsProcessorList([RepetitionPenaltyLogitsProcessor(1.3)] + ([TemperatureLogitsWarper(0.8), TopKLogitsWarper(20)] if sampling else []))
+    dk = {'use_lookahead': True, 'decoding_length': 64, 'branch_length': 12, 'stop_words': {}}
+
+    def plain(model):
+        model.lookahead_cache = LookaheadCache()
+        la = model.lookahead_generation(ids, stopping_criteria=P + n_new, eos_token_id=[None], pad_token_id=0, decoding_kwargs=dict(dk), **extra)
+        return la.tolist(), model.greedy_search(ids, P + n_new, eos_token_id=None, **extra).tolist()
+
+    want = plain(make())
+    model = make()
+    eng = model.engine
+    launches = eng.sample_launches if sampling else eng.penalty_launches
+    crit = StoppingCriteriaList([MaxLengthCriteria(P + n_new), Boom()])
+    for entry in ('lookahead', 'plain'):
+        n0 = launches()
+        with pytest.raises(RuntimeError, match='boom'):
+            if entry == 'lookahead':
+                model.lookahead_generation(ids, logits_processor=procs, stopping_criteria=crit, eos_token_id=[None], pad_token_id=0,
+                                           decoding_kwargs=dict(dk, do_sample=sampling, **({'sample_seed': 7} if sampling else {})), **extra)
+            else:
+                model.greedy_search(ids, P + n_new, eos_token_id=None, logits_processor=procs, do_sample=sampling, stopping_criteria=crit,
+                                    sample_seed=7 if sampling else None, **extra)
+        assert launches() > n0, entry                                     # the request did run on the device stage ...
+        assert eng.repetition_penalty == 1.0 and not getattr(eng, 'sampling', False), entry      # ... and left it switched off
+        counts = (eng.penalty_launches(), eng.sample_launches())
+        assert plain(model) == want, entry
+        assert (eng.penalty_launches(), eng.sample_launches()) == counts, entry
+
+
 # ------------------------------------------------------------------------------------------------ 7. off means off
 def test_without_a_processor_the_stage_is_never_launched():
     shape, model = _decisive_model()
