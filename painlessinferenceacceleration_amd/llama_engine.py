@@ -13,13 +13,14 @@ from lookahead_generation (common/pretrained_model.py:1176-1181).
 import ctypes as C
 import math
 import re
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import lib, check
+from .weight_images import (FP8_MAX, StateDictSource, WeightPacker, dequantize_fp8, fp8_lanes, fp8_row_scale,  # noqa: F401 — re-exported
+                            pack_layer, qkv_mb_workgroups, quantize_fp8, to_lanes)
 
 
 class LlamaShape(object):
@@ -238,54 +239,9 @@ def check_biases(shape, state_dict):
             raise ValueError(f'the state dict carries {k}: {why}; refusing to drop it')
 
 
-FP8_MAX = 448.0          # largest finite e4m3fn value
 PROJECTIONS = ('self_attn.q_proj', 'self_attn.k_proj', 'self_attn.v_proj', 'self_attn.o_proj', 'mlp.gate_proj', 'mlp.up_proj',
                'mlp.down_proj')
 _W16_NAMES = ('storage', 'bf16', 'bfloat16', 'fp16', 'float16')
-
-
-def quantize_fp8(w):
-    """Per-output-row symmetric FP8 (OCP e4m3fn) quantization: s[n] = amax(|W[n, :]|) / 448, q = clamp(W / s, -448, 448) in e4m3fn,
-    so that W'[n][k] = s[n] * q[n][k].  A row whose amax is 0 (lane padding) gets s = 1 and q = 0.  The clamp matters: torch's cast
-    gives NaN above ~464 rather than saturating, and W / s can round just past 448.  -> (q float8_e4m3fn [N, K], s float32 [N])."""
-    w = w.float()
-    amax = w.abs().amax(dim=1)
-    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
-    q = (w / s[:, None]).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
-    return q, s
-
-
-def dequantize_fp8(q, s):
-    """W' = s[n] * q[n][k] in fp32 (what an fp8 engine computes with)."""
-    return q.float() * s.float().reshape(-1, 1)
-
-
-def fp8_row_scale(scale, n_rows, name):
-    """A checkpoint's weight_scale -> fp32 [n_rows]: a scalar per tensor is broadcast to the rows, [N] / [N, 1] is per channel."""
-    scale = scale.detach().float().reshape(-1)
-    if scale.numel() == 1:
-        return scale.expand(n_rows).clone()
-    if scale.numel() != n_rows:
-        raise ValueError(f'{name}: {scale.numel()} scales for {n_rows} rows (per-tensor or per-output-row scales only)')
-    return scale.clone()
-
-
-def fp8_lanes(q, s, n_h, dim, lane_src):
-    """The 128-feature lanes (la_head_lane_map) of an fp8 projection of a model with head_dim < 128: q (uint8 view of the e4m3fn
-    bytes: torch has no fp8 multiply) rows (dim 0: q / k / v) or columns (dim 1: o_proj) spread over the lanes, zero on padding
-    lanes; s (fp32 per output row) follows the rows, padding rows get s = 1.  -> (q, s)."""
-    hd = int((lane_src >= 0).sum())
-    if hd == 128:
-        return q, s
-    src = torch.from_numpy(lane_src.astype(np.int64)).to(q.device)
-    idx = (torch.arange(n_h, device=q.device)[:, None] * hd + src.clamp(min=0)[None, :]).reshape(-1)
-    keep = (src >= 0).repeat(n_h)
-    shape_ = [1, 1]
-    shape_[dim] = -1
-    q = q.index_select(dim, idx) * keep.reshape(shape_).to(q.dtype)
-    if dim == 0:
-        s = torch.where(keep.to(s.device), s.index_select(0, idx.to(s.device)), torch.ones((), dtype=s.dtype, device=s.device))
-    return q, s
 
 
 def check_weight_format(shape, state_dict, weight_format=None, gemm_cfg=None, fuse=0, max_blocks=0):
@@ -344,7 +300,13 @@ DEFAULT_LAB = False      # engines created without lab=... take the product libr
 class LlamaVerifyEngine(object):
     """One GPU: packed weights + KV cache + the captured step graph.  n_slots = 1: one sequence (the bs=1 loop).
     n_slots > 1: the cursor-batch path — every slot owns a max_keys region of the KV cache and the 64 rows of a
-    verify block are shared by the active slots (bstep)."""
+    verify block are shared by the active slots (bstep).
+
+    The weight images are built by weight_images.py (WeightPacker, pack_layer).  Three step families share the engine, each with its
+    own pinned input / result block: the single-sequence step (step / verify_only / commit: _fill writes LA_IN_*, step_finish and
+    commit read LA_ST_*), the cursor batch (bstep / bcommit: LA_BIN_* written and LA_BST_* read in place) and the multi-block step
+    (mstep / mstep_trie / tstep / mstep_trees and their commits: _put_block / _put_trees write LA_MIN_*, _mlaunch queues the pass,
+    _mout_read decodes LA_MOUT_*, _mcommit keeps rows)."""
 
     def __init__(self, shape, state_dict, max_length=2048, device='cuda:0', attn_split=0, gemm_cfg=None,
                  consume_state_dict=False, balanced=True, n_slots=1, fuse=0, max_blocks=0, kv_ring=False, dtype=None, lab=None,
@@ -382,12 +344,11 @@ class LlamaVerifyEngine(object):
         # a dedicated non-default stream: hipStreamBeginCapture is illegal on the legacy NULL stream that
         # torch.cuda.current_stream() returns by default
         self.stream = torch.cuda.Stream(self.device)
-        sp = C.c_void_p(self.stream.cuda_stream)
         # Every kernel lays a head out as a 128-feature lane (RoPE pairs (d, d + 64), 8192-element Q / K / V fragments).  A model whose
         # heads are narrower (LlamaAttention is shape-generic, modeling_llama.py:189-308) runs in the same lanes: its q / k / v rows and
         # o_proj columns are spread over the lanes by la_head_lane_map (feature d -> lane d, its rotary partner d + hd/2 -> lane 64 + d,
-        # zeros elsewhere) BEFORE packing; zero lanes add exact zeros to every dot product, and cfg.head_dim — the real one — sets the
-        # softmax scale.  hd below is the LANE width every size is computed from.
+        # zeros elsewhere) BEFORE packing (weight_images.to_lanes); zero lanes add exact zeros to every dot product, and cfg.head_dim —
+        # the real one — sets the softmax scale.  hd below is the LANE width every size is computed from.
         self.head_dim = int(shape.head_dim)
         if not (8 <= self.head_dim <= 128 and self.head_dim % 2 == 0):
             raise ValueError(f'head_dim={self.head_dim}: even values from 8 to 128 are supported (128-feature lanes)')
@@ -395,241 +356,33 @@ class LlamaVerifyEngine(object):
         lane_src = np.zeros(128, dtype=np.int32)
         check(self._lib.la_head_lane_map(self.head_dim, lane_src.ctypes.data_as(_lib.pi32)), 'head_lane_map')
         self._lane_src = lane_src
+        packer = WeightPacker(self._lib, self.stream, self.device, self.dtype)
+        self._keep = packer.keep
+        src = StateDictSource(state_dict, consume_state_dict, self.device, w8)
 
-        def to_lanes(w, n_h, dim):
-            """[n_h * head_dim, K] rows (dim 0) or [N, n_h * head_dim] columns (dim 1) -> the same with 128 lanes per head"""
-            if self.head_dim == 128:
-                return w
-            w = w.to(self.device)
-            src = torch.from_numpy(lane_src.astype(np.int64)).to(self.device)
-            idx = (torch.arange(n_h, device=self.device)[:, None] * self.head_dim + src.clamp(min=0)[None, :]).reshape(-1)
-            keep = (src >= 0).repeat(n_h)
-            out = w.index_select(dim, idx)
-            shape_ = [1, 1]
-            shape_[dim] = -1
-            return out * keep.reshape(shape_).to(out.dtype)
-        self._keep = []
-        self._img_bytes = 0          # bytes of the packed weight images (+ fp8 scales) built so far: weight_bytes below
-
-        def dev(t):
-            t = t.to(device=self.device, dtype=self.dtype).contiguous()
-            self._keep.append(t)
-            return t
-
-        def pack(w, w2=None):
-            w = w.to(device=self.device, dtype=self.dtype).contiguous()
-            n, k = w.shape
-            if w2 is not None:
-                w2 = w2.to(device=self.device, dtype=self.dtype).contiguous()
-            out = torch.empty((2 if w2 is not None else 1) * n * k, dtype=self.dtype, device=self.device)
-            torch.cuda.synchronize(self.device)          # w was produced on torch's stream
-            check(self._lib.la_pack_weight(sp, w.data_ptr(), w2.data_ptr() if w2 is not None else None, n, k,
-                                     1 if w2 is not None else 0, out.data_ptr()), 'pack_weight')
-            self.stream.synchronize()                    # w / w2 may be freed by the caller right after
-            self._keep.append(out)
-            self._img_bytes += out.numel() * out.element_size()
-            return out
-
-        def take(name):
-            return state_dict.pop(name) if consume_state_dict else state_dict[name]
-
-        def take_fp8(name):
-            """projection `name` (…/q_proj etc.) -> (q as uint8 [N, K] on the device, s fp32 [N]): the checkpoint's own e4m3fn bytes and
-            weight_scale, or quantize_fp8 of a 16/32-bit weight"""
-            w = take(name + '.weight')
-            if w.dtype == torch.float8_e4m3fn:
-                q, sc = w.to(self.device), fp8_row_scale(take(name + '.weight_scale'), w.shape[0], name).to(self.device)
-            else:
-                q, sc = quantize_fp8(w.to(self.device))
-            if consume_state_dict:
-                state_dict.pop(name + '.input_scale', None)        # activations stay 16-bit (W8A16)
-            return q.view(torch.uint8).contiguous(), sc.float().contiguous()
-
-        def keep32(t):
-            t = t.to(device=self.device, dtype=torch.float32).contiguous()
-            self._keep.append(t)
-            self._img_bytes += t.numel() * t.element_size()
-            return t
-
-        def pack8(w, w2=None):
-            n, k = w.shape
-            out = torch.empty((2 if w2 is not None else 1) * n * k, dtype=torch.uint8, device=self.device)
-            torch.cuda.synchronize(self.device)
-            check(self._lib.la_pack_weight_fp8(sp, w.data_ptr(), w2.data_ptr() if w2 is not None else None, n, k,
-                                               1 if w2 is not None else 0, out.data_ptr()), 'pack_weight_fp8')
-            self.stream.synchronize()
-            self._keep.append(out)
-            self._img_bytes += out.numel() * out.element_size()
-            return out
-
-        def lanes8(q, sc, n_h, dim):
-            return fp8_lanes(q, sc, n_h, dim, lane_src)
-
-        # Balanced GEMMs: one workgroup per CU, rows dealt out by la_rowplan (0 = shape not balanceable -> classic grid)
+        # Balanced GEMMs: one workgroup per CU, rows dealt out by la_rowplan (0 = shape not balanceable -> classic grid); the
+        # multi-block step may get a second QKV image over fewer, fuller workgroups (qkv_mb_workgroups)
+        self.qkv_fused = not (gemm_cfg and len(gemm_cfg) > 1 and gemm_cfg[1] < 0)
         n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        n_qkv = (shape.n_heads + 2 * shape.n_kv_heads) * hd
         self.balanced_wg = [0, 0, 0]
-        plans = {}
-        plan_kinds = {}
-        if balanced and not (gemm_cfg and len(gemm_cfg) > 1 and gemm_cfg[1] < 0):
-            for slot, (kind, n_rows) in enumerate([(2, (shape.n_heads + 2 * shape.n_kv_heads) * hd), (1, shape.ffn),
-                                                   (0, shape.vocab)]):
-                nwg = n_cu
-                n = self._lib.la_rowplan(kind, n_rows, nwg, None)
-                if n > 0:
-                    plan = np.zeros(n, dtype=np.int32)
-                    check(min(self._lib.la_rowplan(kind, n_rows, nwg, plan.ctypes.data_as(_lib.pi32)), 0), 'rowplan')
-                    plans[slot] = torch.from_numpy(plan).to(self.device)
-                    plan_kinds[slot] = (kind, n_rows, nwg)
-                    self.balanced_wg[slot] = nwg
-
-        # Multi-block step (192-512 rows, MFMA-bound): when the one-workgroup-per-CU QKV plan leaves the 32-row MFMA blocks less
-        # than 60 % full (GQA: Mistral / Mixtral 24 rows = 12 RoPE pairs per workgroup), a SECOND image over pairs / 32 workgroups
-        # (every block full; 50 MB per layer at the Mistral shape) serves that path: Mistral bs=8 11.26 -> 10.45 ms per step
-        # (scripts/gpu_qkv_wg_ab.sh, profiles/r03_qkv_mb_plan.txt).  LA_QKV_MB_WG overrides (0 = off).
-        self.qkv_mb_wg = 0
-        pairs = (shape.n_heads + 2 * shape.n_kv_heads) * hd // 2
-        if max_blocks > 1 and self.balanced_wg[0] and hd == 128:
-            per_wg = pairs // self.balanced_wg[0]
-            # ... or leaves a pair count per workgroup that is not a multiple of 4 (Llama-2-13B: 30): the RoPE epilogue then stores 4-byte pieces and
-            # 1/16 of the MFMA rows are padding; 240 full workgroups instead: 13B bs=4 10.57 -> 10.45 ms, bs=8 16.00 -> 15.60 (round 6, GPU call 16)
-            want = pairs // 32 if (pairs % 32 == 0 and (per_wg / 32.0 < 0.6 or (per_wg % 4 != 0 and pairs // 32 >= 0.9 * self.balanced_wg[0]))) else 0
-            if os.environ.get('LA_QKV_MB_WG') is not None:
-                want = int(os.environ['LA_QKV_MB_WG'])
-            if want > 0 and want % 16 == 0 and want < self.balanced_wg[0] and pairs % want == 0 and pairs // want <= 32:
-                n = self._lib.la_rowplan(2, 2 * pairs, want, None)
-                if n > 0:
-                    plan = np.zeros(n, dtype=np.int32)
-                    check(min(self._lib.la_rowplan(2, 2 * pairs, want, plan.ctypes.data_as(_lib.pi32)), 0), 'rowplan')
-                    plans['qkv_mb'] = torch.from_numpy(plan).to(self.device)
-                    plan_kinds['qkv_mb'] = (2, 2 * pairs, want)
-                    self.qkv_mb_wg = want
-
-        def pack_planned8(slot, mats):
-            """la_pack_planned_fp8: the planned image with 1-byte elements"""
-            kind, n_rows, nwg = plan_kinds[slot]
-            K = mats[0].shape[1]
-            out = torch.empty(self._lib.la_planned_elems(kind, n_rows, K, nwg), dtype=torch.uint8, device=self.device)
-            torch.cuda.synchronize(self.device)
-            check(self._lib.la_pack_planned_fp8(sp, mats[0].data_ptr(), mats[1].data_ptr() if len(mats) > 1 else None,
-                                                plans[slot].data_ptr(), kind, n_rows, K, nwg, out.data_ptr()), 'pack_planned_fp8')
-            self.stream.synchronize()
-            self._keep.append(out)
-            self._img_bytes += out.numel() * out.element_size()
-            return out
-
-        def pack_planned(slot, mats):
-            """compact workgroup-major packing by the plan (la_pack_planned)"""
-            kind, n_rows, nwg = plan_kinds[slot]
-            mats = [m.to(device=self.device, dtype=self.dtype).contiguous() for m in mats]
-            K = mats[0].shape[1]
-            out = torch.empty(self._lib.la_planned_elems(kind, n_rows, K, nwg), dtype=self.dtype, device=self.device)
-            torch.cuda.synchronize(self.device)
-            check(self._lib.la_pack_planned(sp, mats[0].data_ptr(), mats[1].data_ptr() if len(mats) > 1 else None,
-                                      plans[slot].data_ptr(), kind, n_rows, K, nwg, out.data_ptr()), 'pack_planned')
-            self.stream.synchronize()
-            self._keep.append(out)
-            self._img_bytes += out.numel() * out.element_size()
-            return out
+        if balanced and self.qkv_fused:
+            for slot, (kind, n_rows) in enumerate([(2, n_qkv), (1, shape.ffn), (0, shape.vocab)]):
+                if packer.add_plan(slot, kind, n_rows, n_cu):
+                    self.balanced_wg[slot] = n_cu
+        want = qkv_mb_workgroups(shape.n_heads, shape.n_kv_heads, self.balanced_wg[0], max_blocks, hd)
+        self.qkv_mb_wg = want if want and packer.add_plan('qkv_mb', 2, n_qkv, want) else 0
 
         # rows of [Wq;Wk;Wv] are gathered so that each GEMM workgroup owns RoPE pairs (d, d+64): the QKV epilogue
         # applies RoPE and writes the attention fragments itself (la_gemm64_qkv)
-        self.qkv_fused = not (gemm_cfg and len(gemm_cfg) > 1 and gemm_cfg[1] < 0)
-        n_qkv = (shape.n_heads + 2 * shape.n_kv_heads) * hd
         perm_np = np.zeros(n_qkv, dtype=np.int32)
         check(self._lib.la_qkv_row_perm(shape.n_heads, shape.n_kv_heads, perm_np.ctypes.data_as(_lib.pi32)), 'qkv_row_perm')
-        qkv_perm = torch.from_numpy(perm_np.astype(np.int64)).to(self.device)
-        has_bias = bool(getattr(shape, 'qkv_bias', False))
+        qkv_perm = torch.from_numpy(perm_np.astype(np.int64)).to(self.device) if self.qkv_fused else None
         layers = (_lib.LlamaLayerWeightsC * shape.n_layers)()
         for i in range(shape.n_layers):
-            p = f'model.layers.{i}.'
-            if has_bias:
-                # one lane-ordered vector [q heads | k heads | v heads] x 128 lanes (zeros on padding lanes): the layout every QKV
-                # epilogue reads, whatever the row order of the weight image (la_gemm64_qkv_bias)
-                try:
-                    bq, bk, bv = (take(p + f'self_attn.{n}_proj.bias') for n in 'qkv')
-                except KeyError as e:
-                    raise ValueError(f'shape.qkv_bias is set but the state dict has no {e.args[0]}') from None
-                bias = torch.cat([to_lanes(b.to(self.device).reshape(-1, 1), nh_, 0).reshape(-1)
-                                  for b, nh_ in ((bq, shape.n_heads), (bk, shape.n_kv_heads), (bv, shape.n_kv_heads))])
-                layers[i].qkv_bias = dev(bias).data_ptr()
-            if w8:
-                # fp8: the scales follow the rows through the lanes and the concatenation; the QKV scale vector stays lane-ordered
-                # (slot * 128 + lane) whatever row order the image gets, like the bias
-                parts = [lanes8(*take_fp8(p + f'self_attn.{n}_proj'), nh_, 0)
-                         for n, nh_ in (('q', shape.n_heads), ('k', shape.n_kv_heads), ('v', shape.n_kv_heads))]
-                q8 = torch.cat([a for a, _ in parts], 0)
-                layers[i].wqkv_scale = keep32(torch.cat([b for _, b in parts])).data_ptr()
-                if self.balanced_wg[0]:
-                    layers[i].wqkv = pack_planned8(0, [q8]).data_ptr()
-                else:
-                    layers[i].wqkv = pack8(q8.index_select(0, qkv_perm).contiguous()).data_ptr()
-                del q8, parts
-                qo, so = take_fp8(p + 'self_attn.o_proj')
-                layers[i].wo = pack8(lanes8(qo, so, shape.n_heads, 1)[0].contiguous()).data_ptr()
-                layers[i].wo_scale = keep32(so).data_ptr()
-                (qg, sg), (qu, su) = take_fp8(p + 'mlp.gate_proj'), take_fp8(p + 'mlp.up_proj')
-                layers[i].wgateup = (pack_planned8(1, [qg, qu]) if self.balanced_wg[1] else pack8(qg, qu)).data_ptr()
-                layers[i].wgateup_scale = keep32(torch.cat([sg, su])).data_ptr()
-                qd, sd_ = take_fp8(p + 'mlp.down_proj')
-                layers[i].wdown = pack8(qd).data_ptr()
-                layers[i].wdown_scale = keep32(sd_).data_ptr()
-                del qo, qg, qu, qd
-                layers[i].norm1 = dev(take(p + 'input_layernorm.weight')).data_ptr()
-                layers[i].norm2 = dev(take(p + 'post_attention_layernorm.weight')).data_ptr()
-                torch.cuda.synchronize(self.device)
-                continue
-            qkv = torch.cat([to_lanes(take(p + 'self_attn.q_proj.weight').to(self.device), shape.n_heads, 0),
-                             to_lanes(take(p + 'self_attn.k_proj.weight').to(self.device), shape.n_kv_heads, 0),
-                             to_lanes(take(p + 'self_attn.v_proj.weight').to(self.device), shape.n_kv_heads, 0)], 0)
-            if self.balanced_wg[0]:
-                layers[i].wqkv = pack_planned(0, [qkv]).data_ptr()
-                if self.qkv_mb_wg:
-                    layers[i].wqkv_mb = pack_planned('qkv_mb', [qkv]).data_ptr()
-            else:
-                if self.qkv_fused:
-                    qkv = qkv.index_select(0, qkv_perm)
-                layers[i].wqkv = pack(qkv).data_ptr()
-            del qkv
-            layers[i].wo = pack(to_lanes(take(p + 'self_attn.o_proj.weight'), shape.n_heads, 1)).data_ptr()
-
-            def pack_gateup(gate, up):
-                return (pack_planned(1, [gate, up]) if self.balanced_wg[1] else pack(gate, up)).data_ptr()
-
-            if shape.n_experts > 0:
-                layers[i].router = dev(take(p + 'block_sparse_moe.gate.weight')).data_ptr()
-                gu = (_lib.vp * shape.n_experts)()
-                dn = (_lib.vp * shape.n_experts)()
-                # the expert images of a layer are packed at equal spacing in ONE buffer per projection, which lets the
-                # engine run all experts of a stage in a single launch (la_engine.cpp: ex_merged)
-                gu_all = dn_all = None
-                for e in range(shape.n_experts):
-                    q = p + f'block_sparse_moe.experts.{e}.'
-                    one_gu = pack_planned(1, [take(q + 'w1.weight'), take(q + 'w3.weight')]) if self.balanced_wg[1] \
-                        else pack(take(q + 'w1.weight'), take(q + 'w3.weight'))
-                    one_dn = pack(take(q + 'w2.weight'))
-                    if gu_all is None:
-                        gstride = (one_gu.numel() + 63) // 64 * 64
-                        dstride = (one_dn.numel() + 63) // 64 * 64
-                        gu_all = torch.zeros(shape.n_experts * gstride, dtype=self.dtype, device=self.device)
-                        dn_all = torch.zeros(shape.n_experts * dstride, dtype=self.dtype, device=self.device)
-                    gu_all[e * gstride:e * gstride + one_gu.numel()].copy_(one_gu)
-                    dn_all[e * dstride:e * dstride + one_dn.numel()].copy_(one_dn)
-                    gu[e] = gu_all.data_ptr() + 2 * e * gstride
-                    dn[e] = dn_all.data_ptr() + 2 * e * dstride
-                    self._keep = [t for t in self._keep if t is not one_gu and t is not one_dn]
-                    del one_gu, one_dn
-                torch.cuda.synchronize(self.device)
-                self._keep.extend([gu, dn, gu_all, dn_all])
-                layers[i].ex_gateup = C.cast(gu, C.POINTER(_lib.vp))
-                layers[i].ex_down = C.cast(dn, C.POINTER(_lib.vp))
-            else:
-                layers[i].wgateup = pack_gateup(take(p + 'mlp.gate_proj.weight'), take(p + 'mlp.up_proj.weight'))
-                layers[i].wdown = pack(take(p + 'mlp.down_proj.weight')).data_ptr()
-            layers[i].norm1 = dev(take(p + 'input_layernorm.weight')).data_ptr()
-            layers[i].norm2 = dev(take(p + 'post_attention_layernorm.weight')).data_ptr()
-            torch.cuda.synchronize(self.device)
+            pack_layer(packer, src, shape, i, layers[i], lane_src, qkv_perm)
         self._layers = layers
-        self.embed = dev(take('model.embed_tokens.weight'))
+        self.embed = packer.hold(src.take('model.embed_tokens.weight'))
         self.rope_cos, self.rope_sin = rope_tables(self.head_dim, self.max_pos, shape.rope_theta, self.device, self.dtype)
         if self.head_dim < 128:          # 64 columns per position: the lanes past head_dim / 2 only ever meet zeros
             padc = torch.ones((self.max_pos, 64), dtype=self.dtype, device=self.device)
@@ -639,12 +392,12 @@ class LlamaVerifyEngine(object):
             self.rope_cos, self.rope_sin = padc.contiguous(), pads.contiguous()
         w = _lib.LlamaWeightsC()
         w.embed = self.embed.data_ptr()
-        proj_bytes = self._img_bytes
-        w.lm_head = (pack_planned(2, [take('lm_head.weight')]) if self.balanced_wg[2] else pack(take('lm_head.weight'))).data_ptr()
+        proj_bytes = packer.nbytes
+        w.lm_head = packer.planned_or_plain(2, [src.take('lm_head.weight')]).data_ptr()
         # device bytes of the weights the step streams: projection images (fp8: with their scales), lm_head image, embedding
-        self.weight_bytes = {'projections': proj_bytes, 'lm_head': self._img_bytes - proj_bytes,
+        self.weight_bytes = {'projections': proj_bytes, 'lm_head': packer.nbytes - proj_bytes,
                              'embed': self.embed.numel() * self.embed.element_size()}
-        w.final_norm = dev(take('model.norm.weight')).data_ptr()
+        w.final_norm = packer.hold(src.take('model.norm.weight')).data_ptr()
         w.rope_cos, w.rope_sin = self.rope_cos.data_ptr(), self.rope_sin.data_ptr()
         w.layers = C.cast(layers, C.POINTER(_lib.LlamaLayerWeightsC))
         torch.cuda.synchronize(self.device)
@@ -678,29 +431,30 @@ class LlamaVerifyEngine(object):
         self._h = self._lib.la_llama_create(C.byref(cfg), C.byref(w), self.workspace.data_ptr(), nbytes)
         if not self._h:
             raise _lib.LookaheadHipError(f'la_llama_create: {_lib.last_error()}')
-        self.host_in = torch.zeros(_lib.LA_IN_WORDS, dtype=torch.int32).pin_memory()
-        self.host_out = torch.zeros(_lib.LA_ST_OUTTOK + 64, dtype=torch.int32).pin_memory()
-        self._in_np = self.host_in.numpy()
-        self._out_np = self.host_out.numpy()
-        self._in_rm = self._in_np[_lib.LA_IN_ROWMASK:_lib.LA_IN_ROWMASK + 128].view(np.uint64)
-        self.host_bin = torch.zeros(_lib.LA_BIN_WORDS, dtype=torch.int32).pin_memory()
-        self.host_bout = torch.zeros(_lib.LA_BST_DST, dtype=torch.int32).pin_memory()
-        self._bin_np = self.host_bin.numpy()
-        self._bout_np = self.host_bout.numpy()
-        self._bin_rm = self._bin_np[_lib.LA_BIN_ROWMASK:_lib.LA_BIN_ROWMASK + 128].view(np.uint64)
-        if self.max_blocks:
-            self.host_min = torch.zeros(_lib.LA_MIN_WORDS, dtype=torch.int32).pin_memory()
-            self.host_mout = torch.zeros(_lib.LA_MOUT_DST, dtype=torch.int32).pin_memory()
-            self._min_np = self.host_min.numpy()
-            self._mout_np = self.host_mout.numpy()
-            self._min_rm = self._min_np[_lib.LA_MIN_ROWMASK:_lib.LA_MIN_ROWMASK + 2 * 64 * _lib.LA_MB_MAX].view(np.uint64)
-            self._min_xm = self._min_np[_lib.LA_MIN_XMASK:_lib.LA_MIN_XMASK + 2 * 3 * 64 * _lib.LA_MB_MAX].view(np.uint64).reshape(_lib.LA_MB_MAX * 64, 3)
+        self._alloc_host_blocks()
         self.slot_keys = [0] * self.n_slots
         self.n_keys = 0
         self.repetition_penalty = 1.0
         self._pen_ctx = {}
         self.sampling = False
         self.reset()
+
+    def _alloc_host_blocks(self):
+        """the pinned input / result blocks of the three step families and their numpy views (row masks as uint64)"""
+        def pinned(words):
+            t = torch.zeros(words, dtype=torch.int32).pin_memory()
+            return t, t.numpy()
+        self.host_in, self._in_np = pinned(_lib.LA_IN_WORDS)
+        self.host_out, self._out_np = pinned(_lib.LA_ST_OUTTOK + 64)
+        self._in_rm = self._in_np[_lib.LA_IN_ROWMASK:_lib.LA_IN_ROWMASK + 128].view(np.uint64)
+        self.host_bin, self._bin_np = pinned(_lib.LA_BIN_WORDS)
+        self.host_bout, self._bout_np = pinned(_lib.LA_BST_DST)
+        self._bin_rm = self._bin_np[_lib.LA_BIN_ROWMASK:_lib.LA_BIN_ROWMASK + 128].view(np.uint64)
+        if self.max_blocks:
+            self.host_min, self._min_np = pinned(_lib.LA_MIN_WORDS)
+            self.host_mout, self._mout_np = pinned(_lib.LA_MOUT_DST)
+            self._min_rm = self._min_np[_lib.LA_MIN_ROWMASK:_lib.LA_MIN_ROWMASK + 2 * 64 * _lib.LA_MB_MAX].view(np.uint64)
+            self._min_xm = self._min_np[_lib.LA_MIN_XMASK:_lib.LA_MIN_XMASK + 2 * 3 * 64 * _lib.LA_MB_MAX].view(np.uint64).reshape(_lib.LA_MB_MAX * 64, 3)
 
     def __del__(self):
         h = getattr(self, '_h', None)
@@ -846,16 +600,7 @@ class LlamaVerifyEngine(object):
         root first (la_llama_mcommit)."""
         slots = self._mstep_slots
         assert len(kept) == len(slots)
-        keep = np.full(64 * len(kept), -1, dtype=np.int32)
-        for b, rows in enumerate(kept):
-            for k, r in enumerate(rows):
-                keep[64 * b + int(r)] = k
-        check(self._lib.la_llama_mcommit(self._h, self._sp(), len(kept), keep.ctypes.data_as(_lib.pi32), self.host_mout.data_ptr()),
-              'llama_mcommit')
-        for slot in slots:
-            self.slot_keys[slot] = int(self._mout_np[_lib.LA_MOUT_NKEYS + slot])
-        if 0 in slots:
-            self.n_keys = self.slot_keys[0]
+        self._mcommit(enumerate(kept), len(kept), slots)
 
     def bprefill(self, slot, prompt_ids, eager=False):
         """Prompt of one slot as chains of <= 64 rows; -> first generated token."""
@@ -894,6 +639,75 @@ class LlamaVerifyEngine(object):
         return first
 
     # ---- multi-block step: every block is a full 64-row verify block of its own (la_llama_mstep) ---------------------
+    # the host protocol, once: _put_block / _put_trees write LA_MIN_*, _mlaunch queues the pass, _mout_read decodes LA_MOUT_*, _mcommit keeps rows
+    @staticmethod
+    def _limit(limit):
+        return max(1, min(_lib.LA_MOUT_TOKS, int(limit)))
+
+    def _put_block(self, b, slot, ids, own, mode, lim, ancestors=()):
+        """block b of the pass: its table entry, ids, the row-mask words over its own rows and (LA_MODE_TREE_PIECE) the ancestor words
+        over the earlier blocks of its tree"""
+        a, n = self._min_np, len(ids)
+        a[_lib.LA_MIN_BLK + 4 * b:_lib.LA_MIN_BLK + 4 * b + 4] = (slot, n, mode, lim)
+        a[_lib.LA_MIN_IDS + 64 * b:_lib.LA_MIN_IDS + 64 * b + n] = ids
+        self._min_rm[64 * b:64 * b + n] = own
+        for q, words in enumerate(ancestors):
+            self._min_xm[64 * b:64 * b + n, q] = words
+
+    @staticmethod
+    def _tree(ids, rowmask):
+        """-> (ids int32[T], row masks uint64[T][W], blocks of the tree)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        rm = np.asarray(rowmask, dtype=np.uint64)
+        return ids, rm[:, None] if rm.ndim == 1 else rm, (len(ids) + 63) // 64
+
+    def _put_trees(self, trees, b=0):
+        """trees: (slot, ids int32[T], row masks uint64[T][W], mode, limit word), laid out from block b on: rows 64 p .. 64 p + 63 of a
+        tree form its block p — block 0 in `mode`, the others as LA_MODE_TREE_PIECE; word p of a row's mask is its own-block word,
+        the words q < p its ancestor words over the earlier blocks; a mask with fewer words stands for zeros.  Sets the block count
+        of the pass.  -> [(first block, blocks)] per tree"""
+        spans = []
+        for slot, ids, rm, mode, lim in trees:
+            T, W = rm.shape
+            nb = (T + 63) // 64
+            spans.append((b, nb))
+            for p in range(nb):
+                rows = slice(64 * p, min(T, 64 * p + 64))
+                self._put_block(b, slot, ids[rows], rm[rows, p] if p < W else 0, mode if p == 0 else _lib.LA_MODE_TREE_PIECE, lim,
+                                [rm[rows, q] if q < W else 0 for q in range(p)])
+                b += 1
+        self._min_np[_lib.LA_MIN_NBLK] = b
+        return spans
+
+    def _mlaunch(self, eager):
+        fn = self._lib.la_llama_mstep_eager if eager else self._lib.la_llama_mstep
+        check(fn(self._h, self._sp(), self.host_min.data_ptr(), self.host_mout.data_ptr()), 'llama_mstep')
+
+    def _mout_keys(self, slots):
+        """the cursors of the slots that took part in the pass (or the commit), from the result header"""
+        for slot in slots:
+            self.slot_keys[slot] = int(self._mout_np[_lib.LA_MOUT_NKEYS + slot])
+        if 0 in slots:
+            self.n_keys = self.slot_keys[0]
+
+    def _mout_read(self, slots, blocks):
+        """the result header of a finished pass: new cursors of `slots` -> the emitted tokens of each block in `blocks`"""
+        self._mout_keys(slots)
+        o = self._mout_np
+        return [o[_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b:_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b + int(o[_lib.LA_MOUT_NOUT + b])].tolist()
+                for b in blocks]
+
+    def _mcommit(self, kept_at, n_blocks, slots):
+        """kept_at: (first block of a tree, its rows to keep, root first) -> keep[64 * block + row] = place on the kept path, -1 = drop
+        (la_llama_mcommit over the n_blocks blocks of the last pass), then the new cursors"""
+        keep = np.full(64 * n_blocks, -1, dtype=np.int32)
+        for b0, rows in kept_at:
+            for k, r in enumerate(rows):
+                keep[64 * b0 + int(r)] = k
+        check(self._lib.la_llama_mcommit(self._h, self._sp(), n_blocks, keep.ctypes.data_as(_lib.pi32), self.host_mout.data_ptr()),
+              'llama_mcommit')
+        self._mout_keys(slots)
+
     def mstep(self, blocks, eager=False):
         """blocks: list of (slot, ids, rowmask, mode, limit) — one sequence's draft tree each (mode 0), or consecutive
         64-token pieces of one prompt (mode 1, same slot: a causal chain; every piece but the last holds 64 rows).
@@ -907,26 +721,20 @@ class LlamaVerifyEngine(object):
         the previous step's trie update (LookaheadCache.stream_put_many), the accepted-token gather of an N-rank job
         (AcceptedTokenGather.finish_into_trie), bookkeeping — until mstep_finish()."""
         assert self.max_blocks and 1 <= len(blocks) <= self.max_blocks, 'engine was created with max_blocks < len(blocks)'
-        a = self._min_np
-        a[_lib.LA_MIN_NBLK] = len(blocks)
-        used = {}
+        self._min_np[_lib.LA_MIN_NBLK] = len(blocks)
+        used, rows = {}, {}
         for b, (slot, ids, rowmask, mode, limit) in enumerate(blocks):
             n = len(ids)
             assert 0 <= slot < self.n_slots and 1 <= n <= 64
             prev = used.get(slot)
             assert prev is None or (mode == 1 and prev == (1, 64)), 'several blocks of one slot must form a prefill chain of full blocks'
             used[slot] = (mode, n)
-            a[_lib.LA_MIN_BLK + 4 * b:_lib.LA_MIN_BLK + 4 * b + 4] = (slot, n, mode, max(1, min(_lib.LA_MOUT_TOKS, int(limit))))
-            a[_lib.LA_MIN_IDS + 64 * b:_lib.LA_MIN_IDS + 64 * b + n] = ids
-            self._min_rm[64 * b:64 * b + n] = rowmask
-        rows = {}
+            rows[slot] = rows.get(slot, 0) + n
+            self._put_block(b, slot, ids, rowmask, mode, self._limit(limit))
         self._mstep_slots = [blk[0] for blk in blocks]
-        for slot, ids, _, _, _ in blocks:
-            rows[slot] = rows.get(slot, 0) + len(ids)
         for slot, n in rows.items():
             assert self.slot_keys[slot] + n <= self._capacity(), 'KV cache capacity of the slot exceeded'
-        fn = self._lib.la_llama_mstep_eager if eager else self._lib.la_llama_mstep
-        check(fn(self._h, self._sp(), self.host_min.data_ptr(), self.host_mout.data_ptr()), 'llama_mstep')
+        self._mlaunch(eager)
         self._mstep_pending = (len(blocks), list(rows))
 
     def mstep_finish(self):
@@ -934,13 +742,7 @@ class LlamaVerifyEngine(object):
         nb, slots = self._mstep_pending
         self._mstep_pending = None
         self.stream.synchronize()
-        o = self._mout_np
-        for slot in slots:
-            self.slot_keys[slot] = int(o[_lib.LA_MOUT_NKEYS + slot])
-        if 0 in slots:
-            self.n_keys = self.slot_keys[0]
-        return [o[_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b:_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b + int(o[_lib.LA_MOUT_NOUT + b])].tolist()
-                for b in range(nb)]
+        return self._mout_read(slots, range(nb))
 
     def mstep_trie(self, dev_trie, q0, slots, limits, last_tokens, put_idxs=None, put_branch_length=None):
         """One multi-block verify step whose drafts are the results of the LAST dev_trie.hier_get_dev(...) launch, taken on the
@@ -960,8 +762,7 @@ class LlamaVerifyEngine(object):
         assert self.max_blocks and 1 <= nb <= self.max_blocks
         assert getattr(dev_trie, 'rows', 64) == 64, 'the chained step reads 64-row result blocks (DeviceTrie(max_rows=64), decoding_length <= 64)'
         arr = lambda v: (C.c_int32 * nb)(*[int(x) for x in v])
-        lim = [max(1, min(_lib.LA_MOUT_TOKS, int(x))) for x in limits]
-        check(self._lib.la_llama_mstep_trie(self._h, self._sp(), nb, arr(slots), arr(lim), arr(last_tokens),
+        check(self._lib.la_llama_mstep_trie(self._h, self._sp(), nb, arr(slots), arr([self._limit(x) for x in limits]), arr(last_tokens),
                                       C.c_void_p(dev_trie.out_ids.data_ptr() + 4 * 64 * q0), C.c_void_p(dev_trie.out_rm.data_ptr() + 8 * 64 * q0),
                                       C.c_void_p(dev_trie.out_n.data_ptr() + 4 * q0), self.host_mout.data_ptr()), 'llama_mstep_trie')
         self._trie_wait = None
@@ -985,56 +786,32 @@ class LlamaVerifyEngine(object):
             self._trie_wait.synchronize()
         else:
             self.stream.synchronize()
-        slots = self._trie_slots
-        nb = len(slots)
-        o = self._mout_np
-        self._mstep_slots = list(slots)
-        for slot in slots:
-            self.slot_keys[slot] = int(o[_lib.LA_MOUT_NKEYS + slot])
-        if 0 in slots:
-            self.n_keys = self.slot_keys[0]
-        toks = [o[_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b:_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b + int(o[_lib.LA_MOUT_NOUT + b])].tolist()
-                for b in range(nb)]
-        return toks, [int(o[_lib.LA_MOUT_T + b]) for b in range(nb)]
+        slots = self._mstep_slots = list(self._trie_slots)
+        toks = self._mout_read(slots, range(len(slots)))
+        return toks, [int(self._mout_np[_lib.LA_MOUT_T + b]) for b in range(len(slots))]
 
     # ---- wide trees: one sequence's tree of up to LA_TREE_WIDE_MAX rows as consecutive blocks of one multi-block pass -------
     def tstep(self, ids, rowmask, slot=0, mode=0, limit=None, eager=False):
         """One verify step of ONE sequence whose draft tree may be wider than a 64-row block (the reference grid-searches
         decoding_length up to 256 and publishes its best numbers at decoding_length=128, branch_length=32: README.md:100,
         benchmarks/benchmark.py:256-288).  ids int32[T], rowmask uint64[T] or uint64[T][W] (word w of row i = tree columns
-        64 w ...): rows 64 p .. 64 p + 63 form block p of the pass — block 0 in `mode` (0 verify / 2 forward only), the others as
-        LA_MODE_TREE_PIECE with their ancestor words over the earlier blocks in LA_MIN_XMASK.  -> (emitted tokens, keys kept)."""
-        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        64 w ...; W >= the tree's blocks): rows 64 p .. 64 p + 63 form block p of the pass — block 0 in `mode` (0 verify / 2 forward
+        only), the others as LA_MODE_TREE_PIECE with their ancestor words over the earlier blocks in LA_MIN_XMASK.  limit=None:
+        LA_MOUT_TOKS.  -> (emitted tokens, keys kept)."""
+        ids, rm, nb = self._tree(ids, rowmask)
         T = len(ids)
-        rm = np.asarray(rowmask, dtype=np.uint64)
-        if rm.ndim == 1:
-            rm = rm[:, None]
-        nb = (T + 63) // 64
         assert 1 <= T <= _lib.LA_TREE_WIDE_MAX and nb <= min(self.max_blocks, 4), \
             f'a {T}-row tree needs an engine created with max_blocks >= {nb} (has {self.max_blocks}; at most 4 blocks per tree)'
+        assert rm.shape[1] >= nb, f'a {T}-row tree needs {nb} mask words per row (got {rm.shape[1]})'
         assert 0 <= slot < self.n_slots and mode in (0, 2)
         assert self.slot_keys[slot] + T <= self._capacity(), 'KV cache capacity of the slot exceeded'
-        lim = _lib.LA_MOUT_TOKS if limit is None else max(1, min(_lib.LA_MOUT_TOKS, int(limit)))
-        a = self._min_np
-        a[_lib.LA_MIN_NBLK] = nb
-        for p in range(nb):
-            r0, r1 = 64 * p, min(T, 64 * p + 64)
-            n = r1 - r0
-            a[_lib.LA_MIN_BLK + 4 * p:_lib.LA_MIN_BLK + 4 * p + 4] = (slot, n, mode if p == 0 else _lib.LA_MODE_TREE_PIECE, lim)
-            a[_lib.LA_MIN_IDS + 64 * p:_lib.LA_MIN_IDS + 64 * p + n] = ids[r0:r1]
-            self._min_rm[64 * p:64 * p + n] = rm[r0:r1, p] if p < rm.shape[1] else 0
-            for q in range(p):
-                self._min_xm[64 * p:64 * p + n, q] = rm[r0:r1, q]
+        self._put_trees([(slot, ids, rm, mode, self._limit(_lib.LA_MOUT_TOKS if limit is None else limit))])
         self._mstep_slots = [slot] * nb
-        fn = self._lib.la_llama_mstep_eager if eager else self._lib.la_llama_mstep
-        check(fn(self._h, self._sp(), self.host_min.data_ptr(), self.host_mout.data_ptr()), 'llama_mstep')
+        self._mlaunch(eager)
         self.stream.synchronize()
-        o = self._mout_np
         before = self.slot_keys[slot]
-        self.slot_keys[slot] = int(o[_lib.LA_MOUT_NKEYS + slot])
-        if slot == 0:
-            self.n_keys = self.slot_keys[0]
-        return o[_lib.LA_MOUT_OUTTOK:_lib.LA_MOUT_OUTTOK + int(o[_lib.LA_MOUT_NOUT])].tolist(), self.slot_keys[slot] - before
+        toks, = self._mout_read([slot], [0])
+        return toks, self.slot_keys[slot] - before
 
     def mstep_trees(self, trees, eager=False):
         """Several sequences' draft trees in ONE pass, each tree of up to LA_TREE_WIDE_MAX rows (a batch whose per-sample budget
@@ -1042,75 +819,34 @@ class LlamaVerifyEngine(object):
         lookahead_cache.py:534-541).  trees: list of (slot, ids int32[T], rowmask uint64[T] or uint64[T][W], mode 0 / 2, limit):
         a tree occupies ceil(T / 64) consecutive blocks of the pass (block 0 in `mode`, the others LA_MODE_TREE_PIECE), one tree
         per slot, all blocks together <= max_blocks.  -> list of emitted token lists (tree order)."""
-        a = self._min_np
-        b0s, slots, b = [], set(), 0
+        laid, slots, b = [], [], 0
         for slot, ids, rowmask, mode, limit in trees:
-            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            ids, rm, nb = self._tree(ids, rowmask)
             T = len(ids)
-            rm = np.asarray(rowmask, dtype=np.uint64)
-            if rm.ndim == 1:
-                rm = rm[:, None]
-            nb = (T + 63) // 64
             assert 1 <= T <= _lib.LA_TREE_WIDE_MAX and nb <= 4, f'a tree holds 1..{_lib.LA_TREE_WIDE_MAX} rows (got {T})'
             assert 0 <= slot < self.n_slots and slot not in slots and mode in (0, 2), 'one tree per slot, mode 0 or 2'
             assert self.slot_keys[slot] + T <= self._capacity(), 'KV cache capacity of the slot exceeded'
-            slots.add(slot)
-            lim = max(1, min(_lib.LA_MOUT_TOKS, int(limit)))
-            b0s.append((b, slot))
-            for p_ in range(nb):
-                r0, r1 = 64 * p_, min(T, 64 * p_ + 64)
-                n = r1 - r0
-                a[_lib.LA_MIN_BLK + 4 * b:_lib.LA_MIN_BLK + 4 * b + 4] = (slot, n, mode if p_ == 0 else _lib.LA_MODE_TREE_PIECE, lim)
-                a[_lib.LA_MIN_IDS + 64 * b:_lib.LA_MIN_IDS + 64 * b + n] = ids[r0:r1]
-                self._min_rm[64 * b:64 * b + n] = rm[r0:r1, p_] if p_ < rm.shape[1] else 0
-                for q in range(p_):
-                    self._min_xm[64 * b:64 * b + n, q] = rm[r0:r1, q] if q < rm.shape[1] else 0
-                b += 1
+            slots.append(slot)
+            laid.append((slot, ids, rm, mode, self._limit(limit)))
+            b += nb
         assert self.max_blocks and 1 <= b <= self.max_blocks, f'{b} blocks in one pass need an engine created with max_blocks >= {b}'
-        a[_lib.LA_MIN_NBLK] = b
-        self._mstep_slots = []
-        for (b0, slot), (_, ids, _, _, _) in zip(b0s, trees):
-            self._mstep_slots.extend([slot] * ((len(ids) + 63) // 64))
-        fn = self._lib.la_llama_mstep_eager if eager else self._lib.la_llama_mstep
-        check(fn(self._h, self._sp(), self.host_min.data_ptr(), self.host_mout.data_ptr()), 'llama_mstep')
+        spans = self._put_trees(laid)
+        self._mstep_slots = [slot for slot, (_, nb) in zip(slots, spans) for _ in range(nb)]
+        self._mlaunch(eager)
         self.stream.synchronize()
-        o = self._mout_np
-        for slot in slots:
-            self.slot_keys[slot] = int(o[_lib.LA_MOUT_NKEYS + slot])
-        if 0 in slots:
-            self.n_keys = self.slot_keys[0]
-        return [o[_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b0:_lib.LA_MOUT_OUTTOK + _lib.LA_MOUT_TOKS * b0 + int(o[_lib.LA_MOUT_NOUT + b0])].tolist()
-                for b0, _ in b0s]
+        return self._mout_read(slots, [b0 for b0, _ in spans])
 
     def mcommit_trees(self, kept, n_rows):
         """After mstep_trees(mode 2): kept[i] = the tree rows of tree i to keep (root first, path order), n_rows[i] = its row count
         — the host-walked sequential accept path for several (possibly wide) trees of one pass (la_llama_mcommit)."""
         nbs = [(int(n) + 63) // 64 for n in n_rows]
-        keep = np.full(64 * sum(nbs), -1, dtype=np.int32)
-        b0 = 0
-        for rows, nb in zip(kept, nbs):
-            for k, r in enumerate(rows):
-                keep[64 * b0 + int(r)] = k
-            b0 += nb
-        check(self._lib.la_llama_mcommit(self._h, self._sp(), sum(nbs), keep.ctypes.data_as(_lib.pi32), self.host_mout.data_ptr()),
-              'llama_mcommit')
-        for slot in set(self._mstep_slots):
-            self.slot_keys[slot] = int(self._mout_np[_lib.LA_MOUT_NKEYS + slot])
-        if 0 in self._mstep_slots:
-            self.n_keys = self.slot_keys[0]
+        firsts = [sum(nbs[:i]) for i in range(len(nbs))]
+        self._mcommit(zip(firsts, kept), sum(nbs), set(self._mstep_slots))
 
     def tcommit(self, rows, n_rows):
         """After tstep(mode=2) over an n_rows-row tree: keep the tree rows `rows` (root first, path order) — the host-walked
         sequential accept path on a wide tree (la_llama_mcommit over the tree's blocks)."""
-        nb = (int(n_rows) + 63) // 64
-        keep = np.full(64 * nb, -1, dtype=np.int32)
-        for k, r in enumerate(rows):
-            keep[int(r)] = k
-        check(self._lib.la_llama_mcommit(self._h, self._sp(), nb, keep.ctypes.data_as(_lib.pi32), self.host_mout.data_ptr()), 'llama_mcommit')
-        slot = self._mstep_slots[0]
-        self.slot_keys[slot] = int(self._mout_np[_lib.LA_MOUT_NKEYS + slot])
-        if slot == 0:
-            self.n_keys = self.slot_keys[0]
+        self._mcommit([(0, rows)], (int(n_rows) + 63) // 64, self._mstep_slots[:1])
 
     def mprefill(self, slot, prompt_ids, eager=False):
         """Prompt of one slot in passes of up to max_blocks x 64 tokens (one pass over the weights each); -> first
