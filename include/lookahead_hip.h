@@ -43,7 +43,7 @@ extern "C" {
 #define LA_MOE_MAX_E      8   /* experts per mixture-of-experts layer (Mixtral: 8, top-2) */
 
 /* ABI version: bumped when a signature changes. */
-#define LA_ABI_VERSION  16   /* bumped whenever a struct layout or an entry point changes */
+#define LA_ABI_VERSION  17   /* bumped whenever a struct layout or an entry point changes */
 int          la_abi_version(void);   /* == LA_ABI_VERSION of the header the library was built from */
 /* Storage / MFMA-input type of the loaded library: 0 = bfloat16 (liblookahead_hip.so), 1 = float16 (liblookahead_hip_f16.so, the
  * dtype the reference's examples and benchmarks run, lookahead/benchmarks/llama_benchmark.py:27).  The two libraries are the same
@@ -575,6 +575,35 @@ int la_sample_rows(void* stream, const void* d_logits, int vocab, int n_rows, co
                    float temperature, int top_k, float top_p, const uint32_t* d_bitmap, const int32_t* d_ids, const uint64_t* d_rowmask,
                    const float* d_penalty, int32_t* d_tok, int32_t* d_info);
 int la_sample_bits(void* stream, uint64_t seed, uint32_t stream_id, uint32_t position, int vocab, uint32_t* d_out);
+
+/* ---- log-probabilities on the device --------------------------------------------------------------------------------------------
+ * How likely the model found every token a step emits, as a stage of the verify step AFTER its accept scan: one workgroup per tree
+ * row that the scan KEPT (the root and the accepted rows - their picks are the path tokens and the bonus, exactly the emitted tokens -
+ * or the emitting row of a prefill chain) computes, for the token t in the row's ARGMAX word,
+ *     lp = (x_t - m) - log(sum_v exp(x_v - m))
+ * over x = the row of stored 16-bit logits lm_head wrote, widened to fp32, RAW (before any penalty, temperature or filter), m = the row
+ * maximum: the model's own log-softmax, whether t came from the argmax, the penalised argmax or the sampler.  The sum is the 64-bit
+ * integer mass of the sampling stage (floor(expf(x_v - m) * 2^32), added as integers), so the value has the same bits for the same
+ * logits row on every run and every step form; error against the exact value <= vocab * 2^-32 + 2^-22 |lp| + a few ulps of expf / logf.
+ * The float goes to log[slot][pos + 1], pos = the row's position: the index, in the unpadded sequence, of the token being chosen (the
+ * sampling stage's Philox counter) - no counter, no ordering between workgroups; sibling rows share a position, which is why only kept
+ * rows store.  The log is float[n_slots][max(max_pos, max_keys) + 1], all NaN after la_llama_create / la_llama_reset /
+ * la_llama_reset_slot; the intermediate passes of a prefill chain write prompt positions, which nobody reads.  LIMIT: a kept row whose
+ * pos + 1 lies outside [0, max(max_pos, max_keys)] stores nothing - no error; that position cannot be read either (la_llama_logprobs_read:
+ * LA_E_ARG).  Without kv_ring the KV capacity checks of the steps keep every position inside; with kv_ring the caller keeps positions
+ * below max_pos (the RoPE tables end there as well).  Every step form runs the
+ * stage (la_llama_step graph / eager, la_lookahead_decode, la_llama_bstep, la_llama_mstep modes 0 and 1; mode 2 stores nothing; wide
+ * trees: LA_E_ARG), with and without the penalty and sampling stages; the accept walk, the commit and the result blocks are unchanged.
+ *   la_llama_set_logprobs       per model; enabled = 0 is the default (a step then launches exactly what it launched before the stage
+ *                               existed).  Synchronises `stream`; switching the stage on or off drops the model's captured graphs.
+ *   la_llama_logprob_launches   steps launched with the stage since la_llama_create
+ *   la_llama_logprobs_read      synchronises `stream`, then out[0..n) = log[slot][first_pos .. first_pos + n)
+ *   la_logprob_rows             the row stage alone (unit parity): logits [n_rows <= 64][vocab] of the library's 16-bit type
+ *                               (vocab % 8 == 0), d_tok[n_rows] -> d_out[r] = lp of token d_tok[r] in row r (NaN: token outside the row) */
+int la_llama_set_logprobs(la_llama* m, void* stream, int enabled);
+int la_llama_logprob_launches(la_llama* m);
+int la_llama_logprobs_read(la_llama* m, void* stream, int slot, int first_pos, int n, float* out);
+int la_logprob_rows(void* stream, const void* d_logits, int vocab, int n_rows, const int32_t* d_tok, float* d_out);
 
 /* ---- native decode loop: the per-step host work of lookahead_generation (pretrained_model.py:1172-1240) without the
  * interpreter: hier_get(last max_query_length tokens) -> la_llama_step -> stream_put, until max_length / eos / max_steps.

@@ -19,7 +19,7 @@ LIB_PATH_F16 = LAB_PATH_F16 if LAB_BUILD else os.path.join(_HERE, "liblookahead_
 LA_DTYPE_BF16, LA_DTYPE_F16 = 0, 1
 
 LA_OK = 0
-ABI_VERSION = 16        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
+ABI_VERSION = 17        # LA_ABI_VERSION of include/lookahead_hip.h these bindings were written against
 LA_MODE_INPUT, LA_MODE_OUTPUT, LA_MODE_MIX = 0, 1, 2
 LA_TREE_MAX = 64
 LA_MOE_MAX_E = 8
@@ -253,6 +253,10 @@ PROTOTYPES = {
     "la_llama_sample_launches": (i32, vp),
     "la_sample_rows": (i32, vp, vp, i32, i32, vp, u32, u64, f32, i32, f32, vp, vp, vp, vp, vp, vp),
     "la_sample_bits": (i32, vp, u64, u32, u32, i32, vp),
+    "la_llama_set_logprobs": (i32, vp, vp, i32),
+    "la_llama_logprob_launches": (i32, vp),
+    "la_llama_logprobs_read": (i32, vp, vp, i32, i32, i32, pf32),
+    "la_logprob_rows": (i32, vp, vp, i32, i32, vp, vp),
 }
 
 # the kernel lab (include/lookahead_hip_lab.h): measurement knobs / A/B switches for scripts/ and the bitwise-identity tests — not part

@@ -96,6 +96,12 @@ struct la_llama {
     unsigned samp_stream[LA_SAMP_WORDS - LA_SAMP_STREAM];      // host mirror of the stream words (default: the slot index)
     bool samp_on = false;
     int samp_launches = 0;
+    // log-probabilities on the device (la_logprob.hip): the position-indexed log [n_slots][lp_stride] (NaN = nothing emitted there),
+    // written by the stage every step form launches after its accept scan while the stage is on
+    float* lp_log = nullptr;
+    int lp_stride = 0;
+    bool lp_on = false;
+    int lp_launches = 0;
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -269,6 +275,8 @@ static size_t carve(la_llama* m, char* base) {
     m->pen_bits = cv.take<unsigned>((size_t)m->n_slots * (c.vocab / 32));
     m->pen_val = cv.take<float>(64);
     m->samp_par = cv.take<unsigned>(LA_SAMP_WORDS);
+    m->lp_stride = (c.max_pos > c.max_keys ? c.max_pos : c.max_keys) + 1;
+    m->lp_log = cv.take<float>((size_t)m->n_slots * m->lp_stride);
     return align_up(cv.off, 256);
 }
 
@@ -315,6 +323,12 @@ extern "C" int64_t la_llama_workspace_bytes(const la_llama_config* cfg) {
     tmp.cfg = *cfg;
     resolve_cfg(&tmp);
     return (int64_t)carve(&tmp, nullptr);
+}
+
+// the log-probability log of one slot (slot < 0: of every slot) := NaN (all-ones words)
+static hipError_t lp_clear(la_llama* m, hipStream_t st, int slot) {
+    if (slot < 0) return hipMemsetAsync(m->lp_log, 0xff, (size_t)m->n_slots * m->lp_stride * sizeof(float), st);
+    return hipMemsetAsync(m->lp_log + (size_t)slot * m->lp_stride, 0xff, (size_t)m->lp_stride * sizeof(float), st);
 }
 
 extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_weights* w, void* ws, int64_t ws_bytes) {
@@ -376,6 +390,7 @@ extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_
     for (int i = 0; i < 4; ++i) { m->bgraphs[i] = nullptr; m->bready[i] = false; }
     for (int i = 0; i < 2 * (LA_MB_MAX + 1); ++i) { m->mgraphs[i] = nullptr; m->mready[i] = false; }
     if (m->mb_max && lk_mb_init() != 0) { la_set_error("hipFuncSetAttribute failed for the multi-block kernels"); delete m; return nullptr; }
+    if (lp_clear(m, nullptr, -1) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { la_set_error("la_llama_create: clearing the log-probability log failed"); delete m; return nullptr; }
     return m;
 }
 
@@ -400,6 +415,7 @@ extern "C" int la_llama_reset(la_llama* m, void* stream) {
     HIPCHK(hipMemcpyAsync(m->state + LA_ST_MAXKEYS, &mk, sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(m->bstate, 0, LA_BST_WORDS * sizeof(int), st));
     HIPCHK(hipMemsetAsync(m->pen_bits, 0, (size_t)m->n_slots * (m->cfg.vocab / 32) * sizeof(unsigned), st));
+    HIPCHK(lp_clear(m, st, -1));
     HIPCHK(hipStreamSynchronize(st));
     m->seq_expected = 0;
     if (m->zc_out) m->zc_out[LA_ST_SEQ] = 0;
@@ -414,6 +430,7 @@ extern "C" int la_llama_reset_slot(la_llama* m, void* stream, int slot) {
     const size_t pen_words = (size_t)(m->cfg.vocab / 32);
     if (slot < 0) HIPCHK(hipMemsetAsync(m->pen_bits, 0, (size_t)m->n_slots * pen_words * sizeof(unsigned), st));
     else HIPCHK(hipMemsetAsync(m->pen_bits + (size_t)slot * pen_words, 0, pen_words * sizeof(unsigned), st));
+    HIPCHK(lp_clear(m, st, slot));
     HIPCHK(hipStreamSynchronize(st));
     return LA_OK;
 }
@@ -690,6 +707,13 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
         sa.pen = pen ? 1 : 0; sa.pos = m->pos; sa.params = m->samp_par;
     }
     const bool rows_stage = pen || samp;         // a row stage writes the ARGMAX words
+    // log-probabilities (la_logprob.hip): after the accept scan, the kept rows' picks against the raw logits
+    LpArgs la{};
+    if (m->lp_on) {
+        la.p.kind = batch ? LA_PEN_BATCH : LA_PEN_SINGLE; la.p.vocab = c.vocab; la.p.n_slots = m->n_slots; la.p.nblk = 1;
+        la.p.logits = m->logits; la.p.state = batch ? m->bstate : m->state; la.p.in = m->bin; la.p.out = am_rows;
+        la.pos = m->pos; la.log = m->lp_log; la.stride = m->lp_stride;
+    }
     if (c.balanced_wg[2] > 0) {
         KCHK(lk_gemm64r_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, c.balanced_wg[2], m->logits, m->cand_val, m->cand_idx));
         P(KC_OTHER);
@@ -697,6 +721,7 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
             // argmax finalize + accept walk + result hand-over in ONE launch, the KV commit after it: the host reads the accepted
             // tokens (and starts its trie update / next query) while the commit kernel still runs
             KCHK(lk_step_tail(st, m->cand_val, m->cand_idx, c.balanced_wg[2], m->ids, m->rowmask, m->state, (int*)zc_out));
+            if (m->lp_on) KCHK(lk_logprob_rows(st, la));
             KCHK(lk_kv_commit(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->state, c.n_layers, c.n_kv_heads, m->total_keys, ring));
             P(KC_N);
             return join_pf();
@@ -712,10 +737,12 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
     if (batch) {
         KCHK(lk_accept_scan_b(st, m->bin, m->ids, m->rowmask, m->bstate, m->n_slots, c.max_keys, ring));
         if (pen) KCHK(lk_pen_update(st, pa));
+        if (m->lp_on) KCHK(lk_logprob_rows(st, la));
         KCHK(lk_kv_commit_b(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->bstate, c.n_layers, c.n_kv_heads, m->total_keys));
     } else {
         KCHK(lk_accept_scan(st, m->ids, m->rowmask, m->state));
         if (pen) KCHK(lk_pen_update(st, pa));
+        if (m->lp_on) KCHK(lk_logprob_rows(st, la));
         KCHK(lk_kv_commit(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->state, c.n_layers, c.n_kv_heads, m->total_keys, ring));
         if (zc_out) KCHK(lk_publish(st, m->state, (int*)zc_out));
     }
@@ -770,6 +797,7 @@ static int bstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     while (v < 3 && bsplit > target && bsplit % 2 == 0) { bsplit /= 2; ++v; }
     if (m->pen_on) ++m->pen_launches;
     if (m->samp_on) ++m->samp_launches;
+    if (m->lp_on) ++m->lp_launches;
     if (eager) {
         int rc = enqueue_step(m, st, nullptr, true, nullptr, nullptr, bsplit);
         if (rc != LA_OK) return rc;
@@ -810,6 +838,7 @@ static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = fals
     const la_llama_config& c = m->cfg;
     if (!m->qkv_fused) { la_set_error("mstep needs the fused QKV image (gemm_cfg[1] >= 0)"); return LA_E_ARG; }
     if (m->samp_on && wide) { la_set_error("mstep: device sampling has no wide-tree form (la_llama_set_sampling(enabled = 0) + host walk)"); return LA_E_ARG; }
+    if (m->lp_on && wide) { la_set_error("mstep: device log-probabilities have no wide-tree form (la_llama_set_logprobs(enabled = 0))"); return LA_E_ARG; }
     if (m->pen_on && wide) { la_set_error("mstep: the device repetition penalty has no wide-tree form (la_llama_set_repetition_penalty(1.0) + host walk)"); return LA_E_ARG; }
     const int M = nblk * 64;
     const int npass_rows = (nblk <= 2 ? nblk : ((nblk + 3) / 4) * 4) * 64;     // rows whole passes write (slab stride)
@@ -927,6 +956,13 @@ static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = fals
     KCHK(lk_mb_argmax(st, m->mb_cand_val, m->mb_cand_idx, lk_mb_cand_slots(lwg), nblk, m->mb_out + LA_MOUT_ARGMAX));
     KCHK(lk_mb_accept_scan(st, m->mb_meta, m->mb_ids, m->mb_rowmask, (const uint64_t*)(m->mb_in + LA_MIN_XMASK), m->mb_out + LA_MOUT_ARGMAX, nblk, c.max_keys, c.kv_ring ? 1 : 0, m->bstate, m->mb_out));
     if (m->pen_on) KCHK(lk_pen_update(st, pa));
+    if (m->lp_on) {
+        LpArgs la{};
+        la.p.kind = LA_PEN_MBLOCK; la.p.vocab = c.vocab; la.p.n_slots = m->n_slots; la.p.nblk = nblk; la.p.logits = m->mb_logits;
+        la.p.state = m->mb_out; la.p.meta = m->mb_meta; la.p.out = m->mb_out + LA_MOUT_ARGMAX;
+        la.pos = m->mb_pos; la.log = m->lp_log; la.stride = m->lp_stride;
+        KCHK(lk_logprob_rows(st, la));
+    }
     KCHK(lk_mb_kv_commit(st, m->mb_kfresh, m->mb_vfresh, m->kmain, m->vmain, m->mb_out, nblk, c.n_layers, c.n_kv_heads, m->total_keys));
     return LA_OK;
 }
@@ -942,6 +978,7 @@ static int mstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     HIPCHK(hipMemcpyAsync(m->mb_in, host_in, LA_MIN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
     if (m->pen_on) ++m->pen_launches;
     if (m->samp_on) ++m->samp_launches;
+    if (m->lp_on) ++m->lp_launches;
     if (eager) {
         int rc = enqueue_mstep(m, st, nblk, wide);
         if (rc != LA_OK) return rc;
@@ -977,6 +1014,7 @@ extern "C" int la_llama_mstep_trie(la_llama* m, void* stream, int nblk, const in
     KCHK(lk_mb_fill_from_trie(st, d_ids, d_rowmask, d_n, slots, limits, last_tok, nblk, m->mb_in));
     if (m->pen_on) ++m->pen_launches;
     if (m->samp_on) ++m->samp_launches;
+    if (m->lp_on) ++m->lp_launches;
     const int gi = nblk;
     if (m->mready[gi] && m->mepoch[gi] != g_la_graph_epoch) {
         (void)hipGraphExecDestroy(m->mgraphs[gi]);
@@ -1049,6 +1087,7 @@ extern "C" int la_llama_step(la_llama* m, void* stream, const int32_t* host_in, 
     m->seq_expected += 1;
     if (m->pen_on) ++m->pen_launches;
     if (m->samp_on) ++m->samp_launches;
+    if (m->lp_on) ++m->lp_launches;
     HIPCHK(hipGraphLaunch(long_ctx ? m->graph_long : m->graph_exec, st));
     return LA_OK;
 }
@@ -1077,6 +1116,7 @@ extern "C" int la_llama_step_eager(la_llama* m, void* stream, const int32_t* hos
     HIPCHK(hipMemcpyAsync(m->in, host_in, LA_IN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
     if (m->pen_on) ++m->pen_launches;
     if (m->samp_on) ++m->samp_launches;
+    if (m->lp_on) ++m->lp_launches;
     int rc = enqueue_step(m, st, nullptr, false, nullptr, nullptr, 0, host_in[LA_IN_NKEYS_HINT] + LA_TREE_MAX > m->attn_thr);
     if (rc != LA_OK) return rc;
     if (host_out)
@@ -1323,6 +1363,36 @@ extern "C" int la_llama_sampling_stream(la_llama* m, void* stream, int slot, uin
 
 extern "C" int la_llama_sample_launches(la_llama* m) { return m ? m->samp_launches : LA_E_ARG; }
 
+// ---- log-probabilities on the device (la_logprob.hip) ------------------------------------------------------------------
+extern "C" int la_llama_set_logprobs(la_llama* m, void* stream, int enabled) {
+    if (!m) return LA_E_ARG;
+    const bool on = enabled != 0;
+    if (on && (m->cfg.vocab & 7)) { la_set_error("logprobs: the row stage reads 8 logits per load (vocab % 8 == 0)"); return LA_E_RANGE; }
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // no step in flight runs a graph that is dropped below
+    if (on != m->lp_on) drop_graphs(m);
+    m->lp_on = on;
+    return LA_OK;
+}
+
+extern "C" int la_llama_logprob_launches(la_llama* m) { return m ? m->lp_launches : LA_E_ARG; }
+
+extern "C" int la_llama_logprobs_read(la_llama* m, void* stream, int slot, int first_pos, int n, float* out) {
+    if (!m || slot < 0 || slot >= m->n_slots || first_pos < 0 || n < 0 || (n > 0 && !out) || (int64_t)first_pos + n > m->lp_stride) return LA_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n > 0) HIPCHK(hipMemcpyAsync(out, m->lp_log + (size_t)slot * m->lp_stride + first_pos, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return LA_OK;
+}
+
+extern "C" int la_logprob_rows(void* stream, const void* d_logits, int vocab, int n_rows, const int32_t* d_tok, float* d_out) {
+    if (!d_logits || !d_tok || !d_out || n_rows < 1 || n_rows > LA_TREE_MAX || vocab <= 0 || (vocab & 7)) return LA_E_ARG;
+    LpArgs la{};
+    la.p.kind = LA_PEN_ROWS; la.p.vocab = vocab; la.p.n_slots = 1; la.p.nblk = 1; la.p.n_rows = n_rows;
+    la.p.logits = d_logits; la.p.out = (int*)d_tok; la.out = d_out;
+    KCHK(lk_logprob_rows((hipStream_t)stream, la));
+    return LA_OK;
+}
+
 extern "C" int la_llama_penalty_seed(la_llama* m, void* stream, int slot, const int32_t* tokens, int n) {
     if (!m || slot < 0 || slot >= m->n_slots || n < 0 || (n > 0 && !tokens)) return LA_E_ARG;
     const size_t words = (size_t)(m->cfg.vocab / 32);
@@ -1428,6 +1498,7 @@ extern "C" int la_llama_profile(la_llama* m, void* stream, const int32_t* host_i
         HIPCHK(hipMemcpyAsync(m->state, saved, sizeof(saved), hipMemcpyHostToDevice, st));
         int rc = enqueue_step(m, st, &pf);
         if (rc != LA_OK) return rc;
+        if (m->lp_on) ++m->lp_launches;                     // (a profiled step launches the stage like any other)
         HIPCHK(hipStreamSynchronize(st));
         for (size_t i = 0; i + 1 < pf.used; ++i) {
             float ms = 0;

@@ -191,3 +191,15 @@ struct SampArgs {
 size_t lk_sample_lds_bytes(int vocab, int pen);
 int lk_sample_rows(hipStream_t st, const SampArgs& a);
 int lk_sample_bits(hipStream_t st, unsigned seed_lo, unsigned seed_hi, unsigned stream_id, unsigned position, int vocab, unsigned* out);
+
+// ---- log-probabilities on the device (la_logprob.hip): the raw log-softmax value of the token every KEPT row of a step picked,
+// launched after the accept scan; stored at log[slot][pos[row] + 1] (the position of the token being chosen)
+struct LpArgs {
+    PenArgs p;                        // row addressing (kind, state, in, meta, nblk), logits; p.out = the ARGMAX words (read only);
+                                      // p.state is also where the scan left its keep plan (LA_ST_SRCIDX / LA_BST_DST / LA_MOUT_DST)
+    const int* pos;                   // RoPE position of every row (same index as the logits row)
+    float* log;                       // [n_slots][stride], or null (unit entry): out[row] instead
+    int stride;
+    float* out;
+};
+int lk_logprob_rows(hipStream_t st, const LpArgs& a);

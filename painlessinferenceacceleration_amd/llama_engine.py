@@ -437,6 +437,7 @@ class LlamaVerifyEngine(object):
         self.repetition_penalty = 1.0
         self._pen_ctx = {}
         self.sampling = False
+        self.logprobs_on = False
         self.reset()
 
     def _alloc_host_blocks(self):
@@ -526,6 +527,27 @@ class LlamaVerifyEngine(object):
     def sample_launches(self):
         """steps launched with the sampling stage since the engine was created"""
         return int(self._lib.la_llama_sample_launches(self._h))
+
+    # ---- log-probabilities on the device (csrc/la_logprob.hip) --------------------------------------------------------------
+    def set_logprobs(self, enabled):
+        """The model's own log-softmax value of every token a step emits (raw logits: before any penalty, temperature or filter),
+        taken on the device after the accept scan of every step form (step / decode_native / bstep / mstep, first token after a
+        prefill included) and kept in a position-indexed log per slot; read it with logprobs().  Off (the default): the steps
+        launch exactly what they launch without the stage."""
+        check(self._lib.la_llama_set_logprobs(self._h, self._sp(), 1 if enabled else 0), 'set_logprobs')
+        self.logprobs_on = bool(enabled)
+
+    def logprobs(self, slot, first_pos, n):
+        """np.float32[n]: the log-probabilities of the tokens at positions first_pos .. first_pos + n of `slot`'s unpadded
+        sequence (NaN: no step with the stage on emitted a token there since the slot's last reset).  Waits for the stream."""
+        out = np.empty(int(n), dtype=np.float32)
+        check(self._lib.la_llama_logprobs_read(self._h, self._sp(), int(slot), int(first_pos), int(n), out.ctypes.data_as(_lib.pf32)),
+              'logprobs_read')
+        return out
+
+    def logprob_launches(self):
+        """steps launched with the log-probability stage since the engine was created"""
+        return int(self._lib.la_llama_logprob_launches(self._h))
 
     def penalty_context(self, slot=0):
         """uint32 [vocab / 32]: the context bitmap of `slot` (bit t of word t // 32 <=> token t is in the set)"""

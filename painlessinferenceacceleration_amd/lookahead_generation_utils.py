@@ -143,14 +143,48 @@ def plan_device_stages(logits_processor, engine, eligible, do_sample=False, seed
     return {'penalty': penalty, 'sampling': sampling}
 
 
+def plan_logprobs(requested, engine, host_walk, do_sample=False, seed=None, enabled=True, scores=False, wide=False,
+                  device_trie=False, gather=False):
+    """Whether this request returns per-token log-probabilities (decoding_kwargs['output_logprobs'] / output_logprobs=True): they are
+    taken by a stage of the device step (LlamaVerifyEngine.set_logprobs: csrc/la_logprob.hip), so the request must run the device
+    accept.  -> False when not requested; True when honoured; ValueError naming the condition when the request would take the host
+    walk (`host_walk`: a processor list or sampling that plan_device_stages did not place on the device) or a step form without
+    the stage.  Called before the loop's first engine call."""
+    if not requested:
+        return False
+    why = None
+    if not hasattr(engine, 'set_logprobs'):
+        why = 'this engine has no log-probability stage'
+    elif scores:
+        why = 'output_scores / fresh_scores take the host walk'
+    elif wide:
+        why = 'trees wider than one 64-row block (decoding_length > 64) have no log-probability stage'
+    elif device_trie:
+        why = 'the device trie (device_trie=True) is not served'
+    elif gather:
+        why = "sharded jobs (decoding_kwargs['gather']) are not served"
+    elif host_walk:
+        if do_sample and (isinstance(seed, bool) or not isinstance(seed, int)):
+            why = "do_sample without decoding_kwargs['sample_seed'] takes the host walk"
+        elif not enabled:
+            why = 'device_processors=False together with processors / sampling takes the host walk'
+        else:
+            why = 'this logits-processor list has no device stage and takes the host walk'
+    if why is not None:
+        raise ValueError(f'output_logprobs: {why}')
+    return True
+
+
 @contextmanager
-def device_stages(engine, plan, slots):
+def device_stages(engine, plan, slots, logprobs=False):
     """The stages of `plan` (plan_device_stages; None: nothing) switched on for one request and off again, also after an exception:
     the next request starts without them.  slots: (slot, sampling stream word, token row the slot's penalty context is seeded
     with) per sequence — the batch loops seed with the padded row (what the reference's walk hands the processor); row None: the
-    prefill seeds the context with the prompt itself."""
+    prefill seeds the context with the prompt itself.  logprobs (plan_logprobs): the log-probability stage, likewise."""
     penalty, sampling = (None, None) if plan is None else (plan['penalty'], plan['sampling'])
     try:
+        if logprobs:
+            engine.set_logprobs(True)
         if penalty is not None:
             engine.set_repetition_penalty(penalty)
             for slot, _, row in slots:
@@ -166,6 +200,8 @@ def device_stages(engine, plan, slots):
             engine.set_repetition_penalty(1.0)
         if sampling is not None:
             engine.set_sampling(False)
+        if logprobs:
+            engine.set_logprobs(False)
 
 
 def pick_token(logits_processor, do_sample, ctx_ids, logits_row, device):
@@ -459,5 +495,8 @@ def run_generate(model, batch, inputs, generation_config, logits_processor, stop
                               else getattr(model.generation_config, 'eos_token_id', None),
                               logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
                               stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True),
-                              sample_seed=dk.get('sample_seed', None), **extra)
-    return LookaheadDecoderOnlyOutput(sequences=out, kwargs={}) if ga.return_dict_in_generate else out
+                              sample_seed=dk.get('sample_seed', None), output_logprobs=bool(dk.get('output_logprobs', False)), **extra)
+    out_kwargs = {}
+    if dk.get('output_logprobs', False):          # the plain leg's (sequences, logprobs)
+        out, out_kwargs['logprobs'] = out
+    return LookaheadDecoderOnlyOutput(sequences=out, kwargs=out_kwargs) if ga.return_dict_in_generate else out

@@ -15,7 +15,8 @@ import torch
 
 from . import _lib
 from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, _custom_stop, _max_length_of, _parents_of,  # noqa: F401
-                                          begin_request, device_stages, gc_paused, pick_token, plan_device_stages, run_generate)
+                                          begin_request, device_stages, gc_paused, pick_token, plan_device_stages, plan_logprobs,
+                                          run_generate)
 
 _ONE = np.array([1], dtype=np.uint64)
 
@@ -147,8 +148,31 @@ class LookaheadPreTrainedModel(object):
         assert input_ids.size(0) == 1
         out_device = input_ids.device
         seq = input_ids[0].tolist()
+        n_prompt = len(seq)
         branch_length = decoding_kwargs.get('branch_length', 12)
         eng = self.engine
+        # a list that is exactly one RepetitionPenaltyLogitsProcessor runs as a stage of the device step (the penalised argmax of
+        # every tree row, then the fused accept walk: csrc/la_penalty.hip) and keeps the graph, the fused tail and the native loop;
+        # every other list, sampling, scores, wide trees, the device trie and sharded jobs keep the host walk below
+        # a do_sample request that names decoding_kwargs['sample_seed'] and whose list is [repetition penalty?] + [temperature?,
+        # top-k?, top-p?] runs as the sampling stage of the device step (csrc/la_sample.hip: the seeded draw of every tree row,
+        # then the same accept walk) under the same conditions; without the key it takes the host walk exactly as before
+        do_sample = bool(decoding_kwargs.get('do_sample', False))
+        stages = plan_device_stages(logits_processor, eng, sequential and scores is None and not wide
+                                    and decoding_kwargs.get('gather', None) is None and not decoding_kwargs.get('device_trie', False),
+                                    do_sample=do_sample, seed=decoding_kwargs.get('sample_seed', None),
+                                    enabled=decoding_kwargs.get('device_processors', True))
+        if stages is not None:
+            sequential = False
+        # decoding_kwargs['output_logprobs']: the log-probability stage of the device step (csrc/la_logprob.hip) — honoured whenever
+        # the request runs the device accept, refused (before any engine or trie call) when it would take the host walk
+        want_logprobs = plan_logprobs(decoding_kwargs.get('output_logprobs', False), eng, sequential,
+                                      do_sample=do_sample, seed=decoding_kwargs.get('sample_seed', None),
+                                      enabled=decoding_kwargs.get('device_processors', True),
+                                      scores=scores is not None or bool(decoding_kwargs.get('fresh_scores', False)), wide=wide,
+                                      device_trie=bool(decoding_kwargs.get('device_trie', False)),
+                                      gather=decoding_kwargs.get('gather', None) is not None)
+        logprobs = None
         cap = eng._capacity() if hasattr(eng, '_capacity') else eng.max_keys
         assert stop_max_length + decoding_length + 1 <= cap, f'engine KV capacity {cap} < max_length + decoding_length + 1'
         # Sharded job (distributed.py): decoding_kwargs['gather'] = AcceptedTokenGather(..., b_loc=1, mode='strict' | 'split-phase').
@@ -172,7 +196,6 @@ class LookaheadPreTrainedModel(object):
         eng.reset()
         first = True
         eos_set = set(eos_token_id) if eos_token_id is not None else set()
-        do_sample = bool(decoding_kwargs.get('do_sample', False))
         dm = decoding_kwargs.get('decoding_mode', 'hier')
         dm = dm + '_mix' if dm in ('hier', 'par', 'one') else dm
         native_mode = {'input': 0, 'output': 1, 'mix': 2}.get(dm.split('_')[1], 2)
@@ -181,17 +204,6 @@ class LookaheadPreTrainedModel(object):
         fresh_scores = scores is not None and bool(decoding_kwargs.get('fresh_scores', False))
         if fresh_scores:
             sequential = True            # the host walk sees every logits row it picks from
-        # a list that is exactly one RepetitionPenaltyLogitsProcessor runs as a stage of the device step (the penalised argmax of
-        # every tree row, then the fused accept walk: csrc/la_penalty.hip) and keeps the graph, the fused tail and the native loop;
-        # every other list, sampling, scores, wide trees, the device trie and sharded jobs keep the host walk below
-        # a do_sample request that names decoding_kwargs['sample_seed'] and whose list is [repetition penalty?] + [temperature?,
-        # top-k?, top-p?] runs as the sampling stage of the device step (csrc/la_sample.hip: the seeded draw of every tree row,
-        # then the same accept walk) under the same conditions; without the key it takes the host walk exactly as before
-        stages = plan_device_stages(logits_processor, eng, sequential and scores is None and not wide and gather is None
-                                    and not decoding_kwargs.get('device_trie', False), do_sample=do_sample,
-                                    seed=decoding_kwargs.get('sample_seed', None), enabled=decoding_kwargs.get('device_processors', True))
-        if stages is not None:
-            sequential = False
         native_loop = (not sequential and streamer is None and dm.split('_')[0] == 'hier' and not wide
                        and custom_stop is None and gather is None and scores is None
                        and not decoding_kwargs.get('device_trie', False)
@@ -211,7 +223,7 @@ class LookaheadPreTrainedModel(object):
         last_scores = None         # what the reference's model_kwargs['next_tokens_scores'] holds
         flushed = False
         try:
-            with device_stages(eng, stages, [(0, 0, None)]):      # (row None: prefill seeds the penalty context with the prompt)
+            with device_stages(eng, stages, [(0, 0, None)], logprobs=want_logprobs):      # (row None: prefill seeds the penalty context with the prompt)
                 while True:
                     if first:
                         host_row = sequential or scores is not None      # the last prompt row's logits must stay readable
@@ -320,6 +332,8 @@ class LookaheadPreTrainedModel(object):
                         self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=0)
                         flushed = True
                         break
+                if want_logprobs:          # read once: the steps kept the position-indexed log current on the device
+                    logprobs = [float(x) for x in eng.logprobs(0, n_prompt, len(seq) - n_prompt)]
         finally:
             # an exception mid-generation must not leave this request's stream buffer / input frequencies behind (they would
             # mix into the next request); the reference flushes on the normal path only (pretrained_model.py:1236-1239)
@@ -336,6 +350,8 @@ class LookaheadPreTrainedModel(object):
         sequences = torch.tensor([seq], dtype=torch.long, device=out_device)
         if return_dict_in_generate:
             kwargs = {k: decoding_kwargs[k] for k in ('dls', 'edls', 'fts', 'qts')}
+            if want_logprobs:
+                kwargs['logprobs'] = logprobs
             if scores is not None:
                 scores = tuple(s_.to(out_device) for s_ in scores)
             return LookaheadDecoderOnlyOutput(sequences=sequences, scores=scores, attentions=None, hidden_states=None,
@@ -345,27 +361,31 @@ class LookaheadPreTrainedModel(object):
     # ---------------------------------------------------------------------------------- plain greedy (mode off)
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, eos_token_id=None, logits_processor=None, do_sample=False,
-                      stopping_criteria=None, device_processors=True, sample_seed=None):
+                      stopping_criteria=None, device_processors=True, sample_seed=None, output_logprobs=False):
         """Plain decoding through the same engine (T=1 blocks): the `use_lookahead=False` leg of the reference's
         examples (examples/llama_example.py:39-69).  With a processor list or sampling each token is picked on the host
         from the block's logits row (forward-only step + commit) — except a list that is exactly one repetition penalty, or a
         do_sample request with an int `sample_seed` whose list device_sampling accepts, which run as the device stages
         lookahead_generation uses (device_processors=False: the host pick).  With the same seed this is the no-draft comparator of
-        the sampling lookahead loop: token for token the same sequence."""
+        the sampling lookahead loop: token for token the same sequence.  output_logprobs=True: -> (sequences, list of one
+        log-probability per generated token) from the device stage lookahead_generation uses — its no-draft comparator; a request
+        that would pick on the host is refused (ValueError)."""
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         seq = input_ids[0].tolist()
+        n_prompt = len(seq)
         eng = self.engine
-        eng.reset()
         host_pick = do_sample or (logits_processor is not None and len(logits_processor) > 0)
         stages = plan_device_stages(logits_processor, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
         if stages is not None:
             host_pick = False
+        want_logprobs = plan_logprobs(output_logprobs, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
+        eng.reset()
         custom_stop = _custom_stop(stopping_criteria)        # the caller's criteria besides the length bound, once per token
 
         def pick(row):
             return pick_token(logits_processor, do_sample, seq, eng.logits()[row], eng.device)[0]
 
-        with device_stages(eng, stages, [(0, 0, None)]):
+        with device_stages(eng, stages, [(0, 0, None)], logprobs=want_logprobs):
             tok = eng.prefill(seq, fast=False) if host_pick else eng.prefill(seq)
             if host_pick:
                 tok = pick((len(seq) - 1) % 64)
@@ -379,7 +399,10 @@ class LookaheadPreTrainedModel(object):
                     toks, _ = eng.step(np.asarray([tok], dtype=np.int32), _ONE, mode=0)
                     tok = toks[0]
                 seq.append(tok)
-        return torch.tensor([seq], dtype=torch.long, device=input_ids.device)
+            if want_logprobs:
+                logprobs = [float(x) for x in eng.logprobs(0, n_prompt, len(seq) - n_prompt)]
+        sequences = torch.tensor([seq], dtype=torch.long, device=input_ids.device)
+        return (sequences, logprobs) if want_logprobs else sequences
 
     # ------------------------------------------------------------------------------------------- front door
     def generate(self, inputs=None, generation_config=None, logits_processor=None, stopping_criteria=None,

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, _custom_stop, _parents_of, begin_request, device_stages,
-                                          gc_paused, pick_token, plan_device_stages, run_generate)
+                                          gc_paused, pick_token, plan_device_stages, plan_logprobs, run_generate)
 
 _ONE = np.array([1], dtype=np.uint64)
 
@@ -166,6 +166,31 @@ class LookaheadPreTrainedModel(object):
         if gather is not None:
             assert gather.b_loc == bs, f'AcceptedTokenGather(b_loc={gather.b_loc}) vs a local batch of {bs}'
             assert not decoding_kwargs.get('device_trie', False), 'sharded decoding keeps the trie replicas on the host'
+        # a list that is exactly one RepetitionPenaltyLogitsProcessor runs as a stage of the device step (csrc/la_penalty.hip) and
+        # keeps the fused accept, the async multi-block step and overlap_trie_update; the reference's walk hands the processor
+        # input_ids[b, :cur + i + 2], left pads included, so every slot's context set is seeded with its PADDED row.  Other lists,
+        # sampling, scores, requests in which a sample's tree may be wider than one block, the device trie and sharded jobs keep
+        # the host walk.
+        # a do_sample request with decoding_kwargs['sample_seed'] and a list device_sampling accepts: the sampling stage of the
+        # device step (csrc/la_sample.hip) under the same conditions, stream word of a slot = its batch index
+        do_sample = bool(decoding_kwargs.get('do_sample', False))
+        stages = plan_device_stages(logits_processor, eng, sequential and scores is None and gather is None
+                                    and not decoding_kwargs.get('device_trie', False)
+                                    and min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX, do_sample=do_sample,
+                                    seed=decoding_kwargs.get('sample_seed', None), enabled=decoding_kwargs.get('device_processors', True))
+        if stages is not None:
+            sequential = False
+            decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the penalty / sampling stage)
+        # decoding_kwargs['output_logprobs']: the log-probability stage of the device step (csrc/la_logprob.hip) — honoured whenever
+        # the request runs the device accept, refused (before any engine or trie call) when it would take the host walk
+        want_logprobs = plan_logprobs(decoding_kwargs.get('output_logprobs', False), eng, sequential, do_sample=do_sample,
+                                      seed=decoding_kwargs.get('sample_seed', None), enabled=decoding_kwargs.get('device_processors', True),
+                                      scores=scores is not None or bool(decoding_kwargs.get('fresh_scores', False)),
+                                      wide=min(int(decoding_length), _cap_rows) > _lib.LA_TREE_MAX,
+                                      device_trie=bool(decoding_kwargs.get('device_trie', False)), gather=gather is not None)
+        if want_logprobs:
+            decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the stage)
+        logprobs = None
         gi = (lambda b_: gather.global_index(b_)) if gather is not None else (lambda b_: b_)
         # decoding_kwargs['overlap_trie_update'] (extension, off by default: the reference updates before it queries): the trie update
         # of step k runs on the host AFTER the verify pass of step k + 1 has been queued — drafts see a step's tokens one step later
@@ -186,28 +211,13 @@ class LookaheadPreTrainedModel(object):
             for i in range(bs):                                                 # :1204-1207 (pads included, as there)
                 self.lookahead_cache.put(ids0[i, 1:-1].tolist(), branch_length=branch_length + 1, mode='input', idx=i)
         rows = [ids0[i].tolist() for i in range(bs)]      # padded-coordinate token rows; cursor = len(row) - 1
-        # a list that is exactly one RepetitionPenaltyLogitsProcessor runs as a stage of the device step (csrc/la_penalty.hip) and
-        # keeps the fused accept, the async multi-block step and overlap_trie_update; the reference's walk hands the processor
-        # input_ids[b, :cur + i + 2], left pads included, so every slot's context set is seeded with its PADDED row.  Other lists,
-        # sampling, scores, requests in which a sample's tree may be wider than one block, the device trie and sharded jobs keep
-        # the host walk.
-        # a do_sample request with decoding_kwargs['sample_seed'] and a list device_sampling accepts: the sampling stage of the
-        # device step (csrc/la_sample.hip) under the same conditions, stream word of a slot = its batch index
-        do_sample = bool(decoding_kwargs.get('do_sample', False))
-        stages = plan_device_stages(logits_processor, eng, sequential and scores is None and gather is None
-                                    and not decoding_kwargs.get('device_trie', False)
-                                    and min(int(decoding_length), _cap_rows) <= _lib.LA_TREE_MAX, do_sample=do_sample,
-                                    seed=decoding_kwargs.get('sample_seed', None), enabled=decoding_kwargs.get('device_processors', True))
-        if stages is not None:
-            sequential = False
-            decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the penalty / sampling stage)
         finished_rows = [None] * bs
         batch_indices = list(range(bs))
         eos_set = set(eos_token_id) if eos_token_id is not None else set()
         try:
             ts = time.time()
             eng.reset_slot(-1)
-            with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)]):      # (stream word = batch index, seed = padded row)
+            with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)], logprobs=want_logprobs):      # (stream word = batch index, seed = padded row)
                 # prefill: valid prompt tokens of every sample, packed into shared 64-row chain blocks
                 prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
                 multi = bool(getattr(eng, 'max_blocks', 0))
@@ -423,6 +433,9 @@ class LookaheadPreTrainedModel(object):
                 else:
                     for i in range(bs):                                                 # :1288-1290
                         self.lookahead_cache.stream_put([], branch_length=branch_length + 1, final=True, mode='output', idx=i)
+                if want_logprobs:
+                    # read once: slot i's log is indexed by the position in the UNPADDED sequence; each list is cut at its own stop
+                    logprobs = [[float(x) for x in eng.logprobs(i, len(prompts[i]), len(finished_rows[i]) - P)] for i in range(bs)]
         except BaseException:
             # A failure (or an interrupt) mid-request must not leave the trie with this request's stream buffers / input frequencies, and in a
             # sharded job must not strand the other ranks: they are (or will be) waiting in the per-step collective.  The failing rank keeps
@@ -447,6 +460,8 @@ class LookaheadPreTrainedModel(object):
         sequences = torch.from_numpy(seqs).to(out_device)
         if return_dict_in_generate:
             kwargs = {k: decoding_kwargs[k] for k in ('dls', 'edls', 'fts', 'qts')}
+            if want_logprobs:
+                kwargs['logprobs'] = logprobs
             return LookaheadDecoderOnlyOutput(sequences=sequences, scores=scores, attentions=None, hidden_states=None,
                                               kwargs=kwargs)
         return sequences
@@ -476,17 +491,18 @@ class LookaheadPreTrainedModel(object):
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, attention_mask=None, eos_token_id=None, pad_token_id=0,
                       logits_processor=None, do_sample=False, stopping_criteria=None, device_processors=True,
-                      sample_seed=None):
+                      sample_seed=None, output_logprobs=False):
         """Plain decoding of the whole batch through the same engine (one row per sample per block).  With a processor list or
         sampling every token is picked on the host from the sample's logits row (forward-only step + la_llama_bcommit).
         `stopping_criteria`: the caller's criteria besides the length bound (MaxTimeCriteria, custom ones) are evaluated per
-        row after every token, on the row's own tokens — a row they stop is retired like one that met eos."""
+        row after every token, on the row's own tokens — a row they stop is retired like one that met eos.
+        output_logprobs=True: -> (sequences, one list per sample of one log-probability per generated token) from the device stage
+        lookahead_generation uses — its no-draft comparator; a request that would pick on the host is refused (ValueError)."""
         ids0 = input_ids.cpu().numpy().astype(np.int64)
         bs, P = ids0.shape
         am = np.ones_like(ids0) if attention_mask is None else attention_mask.cpu().numpy().astype(np.int64)
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         eng = self.engine
-        eng.reset_slot(-1)
         prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
         host_pick = do_sample or (logits_processor is not None and len(logits_processor) > 0)
         multi = bool(getattr(eng, 'max_blocks', 0))
@@ -495,9 +511,14 @@ class LookaheadPreTrainedModel(object):
         stages = plan_device_stages(logits_processor, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
         if stages is not None:
             host_pick = False
-        with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)]):
-            return self._greedy_search(eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length,
-                                       eos, pad_token_id, input_ids.device)
+        want_logprobs = plan_logprobs(output_logprobs, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
+        eng.reset_slot(-1)
+        with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)], logprobs=want_logprobs):
+            sequences, n_new = self._greedy_search(eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria,
+                                                   max_length, eos, pad_token_id, input_ids.device)
+            if want_logprobs:
+                return sequences, [[float(x) for x in eng.logprobs(i, len(prompts[i]), n_new[i])] for i in range(bs)]
+            return sequences
 
     def _greedy_search(self, eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria, max_length, eos,
                        pad_token_id, out_device):
@@ -541,7 +562,7 @@ class LookaheadPreTrainedModel(object):
         seqs = np.full((bs, L), pad_token_id, dtype=np.int64)
         for b in range(bs):
             seqs[b, :len(rows[b])] = rows[b]
-        return torch.from_numpy(seqs).to(out_device)
+        return torch.from_numpy(seqs).to(out_device), [len(r) - ids0.shape[1] for r in rows]
 
     def generate(self, inputs=None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  prefix_allowed_tokens_fn=None, synced_gpus=None, assistant_model=None, streamer=None, **kwargs):
