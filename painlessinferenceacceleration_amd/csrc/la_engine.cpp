@@ -22,6 +22,42 @@ extern void la_set_error(const std::string& s);
 #define KCHK(x) do { int e_ = (x); if (e_ != 0) { \
     la_set_error(std::string(#x) + ": launch error " + std::to_string(e_)); return LA_E_HIP; } } while (0)
 
+// One captured step form.  Every graph of a model holds the step as the capture-time knobs (g_la_graph_epoch) and the row stages
+// (drop_graphs) had it: graph_run captures again when either changed.
+struct StepGraph {
+    hipGraphExec_t exec = nullptr;
+    int epoch = 0;                   // g_la_graph_epoch at capture time
+};
+
+static void graph_drop(StepGraph& g) {
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    g.exec = nullptr;
+}
+
+// capture enqueue() on `st` into g; the capture is always ended, a partial graph of a failed enqueue destroyed
+template <typename F> static int graph_capture(StepGraph& g, hipStream_t st, F&& enqueue) {
+    hipGraph_t graph = nullptr;
+    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    hipError_t e = hipStreamEndCapture(st, &graph);
+    if (rc != LA_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    HIPCHK(e);
+    hipGraphExec_t exec = nullptr;
+    HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(graph);
+    g.exec = exec;
+    g.epoch = g_la_graph_epoch;
+    return LA_OK;
+}
+
+// a capture-time knob changed (la_debug_set): capture again; then launch
+template <typename F> static int graph_run(StepGraph& g, hipStream_t st, F&& enqueue) {
+    if (g.exec && g.epoch != g_la_graph_epoch) graph_drop(g);
+    if (!g.exec) { const int rc = graph_capture(g, st, enqueue); if (rc != LA_OK) return rc; }
+    HIPCHK(hipGraphLaunch(g.exec, st));
+    return LA_OK;
+}
+
 struct la_llama {
     la_llama_config cfg;
     std::vector<la_llama_layer_weights> layers;
@@ -62,23 +98,14 @@ struct la_llama {
     uint16_t* mb_xg;
     uint64_t* mb_rowmask;
     size_t mb_fresh_layer;
-    hipGraphExec_t mgraphs[2 * (LA_MB_MAX + 1)];     // [wide][nblk]: passes with wide-tree pieces use the masked attention instantiation
-    bool mready[2 * (LA_MB_MAX + 1)];
-    int mepoch[2 * (LA_MB_MAX + 1)];     // g_la_graph_epoch at capture time, per multi-block graph
-    hipGraphExec_t graph_exec, bgraph_exec;      // bgraph_exec: scratch slot used while capturing a batch variant
-    hipGraphExec_t graph_long = nullptr;         // the single-sequence step with the key-split attention (contexts past attn_thr)
-    bool graph_long_ready = false;
+    StepGraph mgraphs[2 * (LA_MB_MAX + 1)];      // [wide][nblk]: passes with wide-tree pieces use the masked attention instantiation
+    StepGraph sgraphs[2];                        // single-sequence step: [0] single-launch attention, [1] key splits (contexts past attn_thr)
+    StepGraph bgraphs[4];                        // batch step captured per attention key-split count {8, 4, 2, 1}
     int attn_thr = 0;                            // committed keys + 64 up to which the single-launch attention is used (see resolve_cfg)
     int ex_down_ks = 4;                          // K splits of the gathered experts' down projection (multi-block MoE step)
-    hipGraphExec_t bgraphs[4];                  // batch step captured per attention key-split count {8, 4, 2, 1}
-    bool bready[4];
-    int bepoch[4];
-    const int32_t* zc_in;      // pinned host blocks the captured single-sequence graph reads / writes (zero-copy)
+    const int32_t* zc_in;      // pinned host blocks the captured single-sequence graphs read / write (zero-copy)
     int32_t* zc_out;
     int seq_expected;          // value host_out[LA_ST_SEQ] takes when the last launched step has been published
-    bool graph_ready, bgraph_ready;
-    int graph_epoch = 0;       // g_la_graph_epoch at the time the single-sequence step graph was captured
-    hipStream_t graph_stream;
     // forked weight prefetch (round 6): a low-priority side stream that becomes a parallel branch of the captured single-sequence
     // step (k_pf_only launches under the latency-bound kernels), and the two events that fork / join it
     hipStream_t pf_stream = nullptr;
@@ -382,25 +409,24 @@ extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_
     if ((int64_t)need > ws_bytes) { la_set_error("workspace too small"); delete m; return nullptr; }
     m->ws = (char*)ws;
     for (int i = 0; i < LA_SAMP_WORDS - LA_SAMP_STREAM; ++i) m->samp_stream[i] = (unsigned)i;
-    m->graph_ready = m->bgraph_ready = false;
-    m->graph_exec = m->bgraph_exec = nullptr;
-    m->graph_stream = nullptr;
     m->zc_in = nullptr; m->zc_out = nullptr; m->seq_expected = 0;
     if (cfg->n_experts == 0) m->ex_merged = false;
-    for (int i = 0; i < 4; ++i) { m->bgraphs[i] = nullptr; m->bready[i] = false; }
-    for (int i = 0; i < 2 * (LA_MB_MAX + 1); ++i) { m->mgraphs[i] = nullptr; m->mready[i] = false; }
     if (m->mb_max && lk_mb_init() != 0) { la_set_error("hipFuncSetAttribute failed for the multi-block kernels"); delete m; return nullptr; }
     if (lp_clear(m, nullptr, -1) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { la_set_error("la_llama_create: clearing the log-probability log failed"); delete m; return nullptr; }
     return m;
 }
 
+// every captured graph of the model holds the step WITH or WITHOUT each row stage (penalty, sampling, log-probabilities): switching
+// one on / off drops them all (the next step captures again, as after a g_la_graph_epoch change)
+static void drop_graphs(la_llama* m) {
+    for (StepGraph& g : m->sgraphs) graph_drop(g);
+    for (StepGraph& g : m->bgraphs) graph_drop(g);
+    for (StepGraph& g : m->mgraphs) graph_drop(g);
+}
+
 extern "C" void la_llama_destroy(la_llama* m) {
     if (!m) return;
-    if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
-    if (m->graph_long) (void)hipGraphExecDestroy(m->graph_long);
-    if (m->bgraph_exec) (void)hipGraphExecDestroy(m->bgraph_exec);
-    for (int i = 0; i < 4; ++i) if (m->bready[i]) (void)hipGraphExecDestroy(m->bgraphs[i]);
-    for (int i = 0; i < 2 * (LA_MB_MAX + 1); ++i) if (m->mready[i]) (void)hipGraphExecDestroy(m->mgraphs[i]);
+    drop_graphs(m);
     if (m->pf_fork) (void)hipEventDestroy(m->pf_fork);
     if (m->pf_join) (void)hipEventDestroy(m->pf_join);
     if (m->pf_stream) (void)hipStreamDestroy(m->pf_stream);
@@ -452,14 +478,88 @@ struct Prof {
     }
 };
 
+// ---- the row stages after lm_head (la_penalty.hip, la_sample.hip, la_logprob.hip) -----------------------------------------
+// Where a step form keeps its rows: everything the row stages of the single-sequence step (LA_PEN_SINGLE), the cursor batch
+// (LA_PEN_BATCH) and the multi-block step (LA_PEN_MBLOCK) are told about the form.
+struct StepRows {
+    int kind, nblk;
+    const void* logits;
+    const int *ids, *pos;
+    const uint64_t* rowmask;
+    const int* state;          // LA_ST_* / LA_BST_* / LA_MOUT_* block
+    const int* in;             // BATCH: LA_BIN_* block (per-slot modes)
+    const int* meta;           // MBLOCK: block meta records
+    int* argmax;               // the ARGMAX words inside `state`
+};
+
+static StepRows step_rows(la_llama* m, int kind, int nblk) {
+    if (kind == LA_PEN_MBLOCK)
+        return StepRows{kind, nblk, m->mb_logits, m->mb_ids, m->mb_pos, m->mb_rowmask, m->mb_out, nullptr, m->mb_meta, m->mb_out + LA_MOUT_ARGMAX};
+    if (kind == LA_PEN_BATCH)
+        return StepRows{kind, 1, m->logits, m->ids, m->pos, m->rowmask, m->bstate, m->bin, nullptr, m->bstate + LA_BST_ARGMAX};
+    return StepRows{kind, 1, m->logits, m->ids, m->pos, m->rowmask, m->state, nullptr, nullptr, m->state + LA_ST_ARGMAX};
+}
+
+// Row addressing, logits and ARGMAX words: what every stage reads.  `context`: + the context sets, the penalty word and the path
+// tokens of every row (k_pen_argmax, k_pen_update, k_sample_rows); without, p.rowmask is null and pen_row reads no path.
+static PenArgs pen_args(const la_llama* m, const StepRows& r, bool context = true) {
+    PenArgs pa{};
+    pa.kind = r.kind; pa.vocab = m->cfg.vocab; pa.n_slots = m->n_slots; pa.nblk = r.nblk;
+    pa.logits = r.logits; pa.state = r.state; pa.in = r.in; pa.meta = r.meta; pa.out = r.argmax;
+    if (context) { pa.bitmaps = m->pen_bits; pa.penalty = m->pen_val; pa.ids = r.ids; pa.rowmask = (const unsigned long long*)r.rowmask; }
+    return pa;
+}
+
+// The pick of every live row, between lm_head and the accept scan: the sampled token (the stage applies the penalty itself, so it
+// gets the context fields whether it reads them or not), else the penalised argmax; *own = neither stage is on and the caller runs
+// its form's own candidate reduction.
+static int pick_rows(la_llama* m, hipStream_t st, const StepRows& r, bool* own) {
+    *own = !m->samp_on && !m->pen_on;
+    if (m->samp_on) {
+        SampArgs sa{};
+        sa.p = pen_args(m, r); sa.pen = m->pen_on ? 1 : 0; sa.pos = r.pos; sa.params = m->samp_par;
+        KCHK(lk_sample_rows(st, sa));
+    } else if (m->pen_on) KCHK(lk_pen_argmax(st, pen_args(m, r)));
+    return LA_OK;
+}
+
+// After the accept scan, before the KV commit: the emitted tokens join the slot's context set, then the kept rows' picks are scored
+// against the raw logits.
+static int after_scan(la_llama* m, hipStream_t st, const StepRows& r) {
+    if (m->pen_on) KCHK(lk_pen_update(st, pen_args(m, r)));
+    if (m->lp_on) {
+        LpArgs la{};
+        la.p = pen_args(m, r, false); la.pos = r.pos; la.log = m->lp_log; la.stride = m->lp_stride;
+        KCHK(lk_logprob_rows(st, la));
+    }
+    return LA_OK;
+}
+
+// a step entry point launches every stage that is on
+static void count_stages(la_llama* m) {
+    if (m->pen_on) ++m->pen_launches;
+    if (m->samp_on) ++m->samp_launches;
+    if (m->lp_on) ++m->lp_launches;
+}
+
+// which form of the 64-row step enqueue_step lays down
+struct StepForm {
+    bool batch = false;                  // the cursor batch (LA_BIN_* / LA_BST_*) instead of the single sequence
+    const int32_t* zc_in = nullptr;      // single sequence: pinned host blocks read / published in place (the captured graphs)
+    int32_t* zc_out = nullptr;
+    int bsplit = 0;                      // batch: attention key splits (0: the configured count)
+    bool long_ctx = false;               // single sequence: key-split attention (contexts past attn_thr)
+    bool fork = false;                   // forked weight prefetch (capture only)
+};
+
 // enqueue every kernel of one block on `st` (used eagerly, under graph capture, and by the profiler)
-static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = false, const int32_t* zc_in = nullptr,
-                        int32_t* zc_out = nullptr, int bsplit = 0, bool long_ctx = false, bool fork = false) {
+static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, const StepForm& form) {
     const la_llama_config& c = m->cfg;
+    const bool batch = form.batch, long_ctx = form.long_ctx;
     // fp8 images: every prefetch descriptor (lk_pf_planned / lk_pf_classic) counts 16-bit bytes and would read past an fp8 image, and
     // the lab's o_proj forms read 16-bit weights: all of them stay off, whatever the lab knobs say
     const bool w8 = c.weight_format == 1;
-    if (w8) fork = false;
+    const bool fork = form.fork && !w8;
     // Forked weight prefetch: `fork_pf(d)` makes the side stream wait for everything queued on `st` so far and launches the
     // prefetch workgroups of descriptor d there — under stream capture a parallel branch of the graph that starts when the step
     // reaches this point and is joined at the end of the step only (nothing waits for a prefetch: it writes nothing).
@@ -483,12 +583,23 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
         forked = false;
         return LA_OK;
     };
+    // a fork point: the side stream waits once, for the first descriptor of the point that has anything to prefetch
+    auto fork_point = [&](std::initializer_list<PfDesc> descs) -> int {
+        bool first = true;
+        for (const PfDesc& d : descs) {
+            if (!d.base) continue;
+            const int rc = fork_pf(d, first);
+            if (rc != LA_OK) return rc;
+            first = false;
+        }
+        return LA_OK;
+    };
     const int* fk = g_la_fork_pf;
     const int ring = c.kv_ring ? c.max_keys : 0;          // sliding-window ring: position p of a sequence lives in row p mod max_keys
     auto P = [&](int cls) { if (pf) pf->mark(cls); };
     P(KC_OTHER);
     if (batch) KCHK(lk_build_tree_inputs_b(st, m->bin, m->bstate, m->pos, m->rowmask, m->ids));
-    else if (g_la_split_head_tail) KCHK(lk_build_tree_inputs(st, zc_in ? (const int*)zc_in : m->in, m->state, m->pos, m->rowmask, m->ids));
+    else if (g_la_split_head_tail) KCHK(lk_build_tree_inputs(st, form.zc_in ? (const int*)form.zc_in : m->in, m->state, m->pos, m->rowmask, m->ids));
     const int cf = c.norm_cast_first;
     if (m->fuse) HIPCHK(hipMemsetAsync(m->fuse_cnt, 0, sizeof(int) * 3 * c.n_layers, st));
     // Idle-window weight prefetch (la_kernels.h, PfDesc): the row kernels and the attention combine carry extra workgroups that
@@ -507,7 +618,7 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
     // single-sequence step: input expansion + embedding row kernel in ONE launch (k_step_head); la_debug_set key 14 = 1 restores
     // the separate kernels of rounds 1-2 (A/B measurements)
     if (!batch && !g_la_split_head_tail)
-        KCHK(lk_step_head(st, zc_in ? (const int*)zc_in : m->in, m->state, m->pos, m->rowmask, m->ids, m->w.embed, m->layers[0].norm1,
+        KCHK(lk_step_head(st, form.zc_in ? (const int*)form.zc_in : m->in, m->state, m->pos, m->rowmask, m->ids, m->w.embed, m->layers[0].norm1,
                           c.hidden, c.rms_eps, m->h, m->xp, cf, &pd, m->norm_gran, 2 * c.n_layers * 256));
     else
         KCHK(lk_embed_norm(st, m->w.embed, m->ids, m->layers[0].norm1, c.hidden, c.rms_eps, m->h, m->xp, cf, &pd));
@@ -536,16 +647,17 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
         }
         P(KC_ATTN);
         if (fork && c.n_experts == 0) {
-            PfDesc fd{};
-            bool first = true;
-            if (fk[0] > 0) { lk_pf_classic(&fd, L.wo, c.hidden, m->o_k, m->o_rb, m->o_ks, fk[0], 0, nullptr); if (fd.base) { int rc = fork_pf(fd, first); if (rc != LA_OK) return rc; first = false; } }
-            if (fk[1] > 0 && c.balanced_wg[1] > 0) { lk_pf_planned(&fd, L.wgateup, 1, c.ffn, c.hidden, c.balanced_wg[1], fk[1], 0, nullptr); if (fd.base) { int rc = fork_pf(fd, first); if (rc != LA_OK) return rc; first = false; } }
+            PfDesc fo{}, fg{};
+            if (fk[0] > 0) lk_pf_classic(&fo, L.wo, c.hidden, m->o_k, m->o_rb, m->o_ks, fk[0], 0, nullptr);
+            if (fk[1] > 0 && c.balanced_wg[1] > 0) lk_pf_planned(&fg, L.wgateup, 1, c.ffn, c.hidden, c.balanced_wg[1], fk[1], 0, nullptr);
+            const int rc = fork_point({fo, fg});
+            if (rc != LA_OK) return rc;
         }
         pd = PfDesc{};
         if (pf_kib > 0) lk_pf_classic(&pd, L.wo, c.hidden, m->o_k, m->o_rb, m->o_ks, pf_kib, pf_dly, nullptr);
         if (batch)
             KCHK(lk_tree_attn_b(st, m->qf, m->kmain + (size_t)l * m->kv_layer_elems, m->vmain + (size_t)l * m->kv_layer_elems,
-                                kf, vf, m->rowmask, m->bstate, c.n_heads, c.n_kv_heads, c.max_keys, m->n_slots, bsplit > 0 ? bsplit : m->nsplit,
+                                kf, vf, m->rowmask, m->bstate, c.n_heads, c.n_kv_heads, c.max_keys, m->n_slots, form.bsplit > 0 ? form.bsplit : m->nsplit,
                                 m->opart, m->mpart, m->lpart, m->attn_xp, c.sliding_window, ring, &pd, c.head_dim));
 #if LA_LAB
         else if (g_la_attn_merge_ns > 0 && !w8 && !long_ctx && c.n_experts == 0 && c.sliding_window <= 0 && (m->o_k / 16) / m->o_ks == 64 &&
@@ -578,10 +690,11 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
 #endif
         P(KC_OTHER);
         if (fork && c.n_experts == 0) {
-            PfDesc fd{};
-            bool first = true;
-            if (fk[2] > 0 && c.balanced_wg[1] > 0) { lk_pf_planned(&fd, L.wgateup, 1, c.ffn, c.hidden, c.balanced_wg[1], fk[2], 0, nullptr); if (fd.base) { int rc = fork_pf(fd, first); if (rc != LA_OK) return rc; first = false; } }
-            if (fk[4] > 0) { lk_pf_classic(&fd, L.wdown, c.hidden, c.ffn, m->down_rb, m->down_ks, fk[4], 0, nullptr); if (fd.base) { int rc = fork_pf(fd, first); if (rc != LA_OK) return rc; first = false; } }
+            PfDesc fg{}, fdn{};
+            if (fk[2] > 0 && c.balanced_wg[1] > 0) lk_pf_planned(&fg, L.wgateup, 1, c.ffn, c.hidden, c.balanced_wg[1], fk[2], 0, nullptr);
+            if (fk[4] > 0) lk_pf_classic(&fdn, L.wdown, c.hidden, c.ffn, m->down_rb, m->down_ks, fk[4], 0, nullptr);
+            const int rc = fork_point({fg, fdn});
+            if (rc != LA_OK) return rc;
         }
         const void* nw = (l + 1 < nl) ? m->layers[l + 1].norm1 : m->w.final_norm;
         if (c.n_experts > 0) {
@@ -669,7 +782,8 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
             PfDesc fd{};
             if (l + 1 < nl) { if (c.balanced_wg[0] > 0) lk_pf_planned(&fd, m->layers[l + 1].wqkv, 2, (c.n_heads + 2 * c.n_kv_heads) * 128, c.hidden, c.balanced_wg[0], fk[3], 0, nullptr); }
             else if (c.balanced_wg[2] > 0) lk_pf_planned(&fd, m->w.lm_head, 0, c.vocab, c.hidden, c.balanced_wg[2], fk[3], 0, nullptr);
-            if (fd.base) { int rc = fork_pf(fd, true); if (rc != LA_OK) return rc; }
+            const int rc = fork_point({fd});
+            if (rc != LA_OK) return rc;
         }
     after_down:
         if (!((m->fuse & 2) && l + 1 < nl)) {        // otherwise fused into the next layer's QKV launch
@@ -686,96 +800,58 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, bool batch = fals
         }
     }
     P(KC_LMHEAD);
-    int* am_rows = batch ? m->bstate + LA_BST_ARGMAX : m->state + LA_ST_ARGMAX;
-    // repetition penalty (la_penalty.hip): the penalised argmax of every live row over the logits lm_head has just written takes the
-    // place of the candidate reduction, the walk kernels run as they are, then the emitted tokens join the slot's context set
-    const bool pen = m->pen_on;
-    PenArgs pa{};
-    if (pen) {
-        pa.kind = batch ? LA_PEN_BATCH : LA_PEN_SINGLE; pa.vocab = c.vocab; pa.n_slots = m->n_slots; pa.nblk = 1;
-        pa.logits = m->logits; pa.bitmaps = m->pen_bits; pa.penalty = m->pen_val; pa.ids = m->ids;
-        pa.rowmask = (const unsigned long long*)m->rowmask; pa.state = batch ? m->bstate : m->state; pa.in = m->bin; pa.out = am_rows;
-    }
-    // sampling (la_sample.hip): the sampled token of every live row takes the place of the candidate reduction AND of k_pen_argmax
-    // (the stage applies the penalty itself); the walk kernels and k_pen_update run as they are
-    const bool samp = m->samp_on;
-    SampArgs sa{};
-    if (samp) {
-        sa.p.kind = batch ? LA_PEN_BATCH : LA_PEN_SINGLE; sa.p.vocab = c.vocab; sa.p.n_slots = m->n_slots; sa.p.nblk = 1;
-        sa.p.logits = m->logits; sa.p.bitmaps = m->pen_bits; sa.p.penalty = m->pen_val; sa.p.ids = m->ids;
-        sa.p.rowmask = (const unsigned long long*)m->rowmask; sa.p.state = batch ? m->bstate : m->state; sa.p.in = m->bin; sa.p.out = am_rows;
-        sa.pen = pen ? 1 : 0; sa.pos = m->pos; sa.params = m->samp_par;
-    }
-    const bool rows_stage = pen || samp;         // a row stage writes the ARGMAX words
-    // log-probabilities (la_logprob.hip): after the accept scan, the kept rows' picks against the raw logits
-    LpArgs la{};
-    if (m->lp_on) {
-        la.p.kind = batch ? LA_PEN_BATCH : LA_PEN_SINGLE; la.p.vocab = c.vocab; la.p.n_slots = m->n_slots; la.p.nblk = 1;
-        la.p.logits = m->logits; la.p.state = batch ? m->bstate : m->state; la.p.in = m->bin; la.p.out = am_rows;
-        la.pos = m->pos; la.log = m->lp_log; la.stride = m->lp_stride;
-    }
-    if (c.balanced_wg[2] > 0) {
-        KCHK(lk_gemm64r_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, c.balanced_wg[2], m->logits, m->cand_val, m->cand_idx));
-        P(KC_OTHER);
-        if (!rows_stage && !batch && !g_la_split_head_tail) {
-            // argmax finalize + accept walk + result hand-over in ONE launch, the KV commit after it: the host reads the accepted
-            // tokens (and starts its trie update / next query) while the commit kernel still runs
-            KCHK(lk_step_tail(st, m->cand_val, m->cand_idx, c.balanced_wg[2], m->ids, m->rowmask, m->state, (int*)zc_out));
-            if (m->lp_on) KCHK(lk_logprob_rows(st, la));
-            KCHK(lk_kv_commit(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->state, c.n_layers, c.n_kv_heads, m->total_keys, ring));
-            P(KC_N);
-            return join_pf();
-        }
-        if (!rows_stage) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, c.balanced_wg[2], am_rows));
+    // The tail of every step form: lm_head, the pick of every live row (a row stage, or the form's own candidate reduction), the
+    // accept scan, the stages behind it (after_scan), the KV commit.
+    const StepRows rows = step_rows(m, batch ? LA_PEN_BATCH : LA_PEN_SINGLE, 1);
+    const bool planned = c.balanced_wg[2] > 0;
+    if (planned) KCHK(lk_gemm64r_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, c.balanced_wg[2], m->logits, m->cand_val, m->cand_idx));
+    else KCHK(lk_gemm64_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, m->lm_rb, m->logits, m->cand_val, m->cand_idx));
+    P(KC_OTHER);
+    bool own = false;
+    int rc = pick_rows(m, st, rows, &own);
+    if (rc != LA_OK) return rc;
+    const bool fused_tail = own && planned && !batch && !g_la_split_head_tail;
+    if (fused_tail) {
+        // argmax finalize + accept walk + result hand-over in ONE launch, the KV commit after it: the host reads the accepted
+        // tokens (and starts its trie update / next query) while the commit kernel still runs
+        KCHK(lk_step_tail(st, m->cand_val, m->cand_idx, c.balanced_wg[2], m->ids, m->rowmask, m->state, (int*)form.zc_out));
     } else {
-        KCHK(lk_gemm64_logits(st, m->w.lm_head, m->xp, c.vocab, c.hidden, m->lm_rb, m->logits, m->cand_val, m->cand_idx));
-        P(KC_OTHER);
-        if (!rows_stage) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, lk_logits_cand_slots(c.vocab, m->lm_rb), am_rows));
+        if (own) KCHK(lk_argmax_finalize(st, m->cand_val, m->cand_idx, planned ? c.balanced_wg[2] : lk_logits_cand_slots(c.vocab, m->lm_rb), rows.argmax));
+        if (batch) KCHK(lk_accept_scan_b(st, m->bin, m->ids, m->rowmask, m->bstate, m->n_slots, c.max_keys, ring));
+        else KCHK(lk_accept_scan(st, m->ids, m->rowmask, m->state));
     }
-    if (samp) KCHK(lk_sample_rows(st, sa));
-    else if (pen) KCHK(lk_pen_argmax(st, pa));
-    if (batch) {
-        KCHK(lk_accept_scan_b(st, m->bin, m->ids, m->rowmask, m->bstate, m->n_slots, c.max_keys, ring));
-        if (pen) KCHK(lk_pen_update(st, pa));
-        if (m->lp_on) KCHK(lk_logprob_rows(st, la));
-        KCHK(lk_kv_commit_b(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->bstate, c.n_layers, c.n_kv_heads, m->total_keys));
-    } else {
-        KCHK(lk_accept_scan(st, m->ids, m->rowmask, m->state));
-        if (pen) KCHK(lk_pen_update(st, pa));
-        if (m->lp_on) KCHK(lk_logprob_rows(st, la));
-        KCHK(lk_kv_commit(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->state, c.n_layers, c.n_kv_heads, m->total_keys, ring));
-        if (zc_out) KCHK(lk_publish(st, m->state, (int*)zc_out));
-    }
+    rc = after_scan(m, st, rows);
+    if (rc != LA_OK) return rc;
+    if (batch) KCHK(lk_kv_commit_b(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->bstate, c.n_layers, c.n_kv_heads, m->total_keys));
+    else KCHK(lk_kv_commit(st, m->kfresh, m->vfresh, m->kmain, m->vmain, m->state, c.n_layers, c.n_kv_heads, m->total_keys, ring));
+    if (!batch && !fused_tail && form.zc_out) KCHK(lk_publish(st, m->state, (int*)form.zc_out));
     P(KC_N);
     return join_pf();
 }
 
-static int build_graph(la_llama* m, hipStream_t st, bool batch = false, const int32_t* zc_in = nullptr,
-                       int32_t* zc_out = nullptr, int bsplit = 0, bool long_ctx = false) {
-    hipGraph_t g = nullptr;
-    bool fork = false;
-    if (!batch) for (int i = 0; i < 5; ++i) fork = fork || g_la_fork_pf[i] > 0;
-    if (fork && !m->pf_stream) {
+// capture one of the two single-sequence forms over the caller's pinned blocks
+static int capture_single(la_llama* m, hipStream_t st, const int32_t* zc_in, int32_t* zc_out, bool long_ctx) {
+    StepForm form;
+    form.zc_in = zc_in; form.long_ctx = long_ctx;
+    for (int i = 0; i < 5; ++i) form.fork = form.fork || g_la_fork_pf[i] > 0;
+    if (form.fork && !m->pf_stream) {        // the side stream and its events exist before the capture begins
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);          // lo = the numerically largest value = the LOWEST priority
         HIPCHK(hipStreamCreateWithPriority(&m->pf_stream, hipStreamNonBlocking, lo));
         HIPCHK(hipEventCreateWithFlags(&m->pf_fork, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&m->pf_join, hipEventDisableTiming));
     }
-    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     // measurement knob (la_debug_set key 11): the single-sequence graph holds the step n times (the same input block each time, only
     // the last repetition publishes) — what a launch costs beyond its kernels shows as time per repetition vs n
-    const int reps = (!batch && g_la_graph_reps > 1) ? g_la_graph_reps : 1;
-    int rc = LA_OK;
-    for (int r = 0; r < reps && rc == LA_OK; ++r) rc = enqueue_step(m, st, nullptr, batch, zc_in, r + 1 == reps ? zc_out : nullptr, bsplit, long_ctx, fork);
-    hipError_t e = hipStreamEndCapture(st, &g);
-    if (rc != LA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-    HIPCHK(e);
-    HIPCHK(hipGraphInstantiate(batch ? &m->bgraph_exec : (long_ctx ? &m->graph_long : &m->graph_exec), g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
-    (batch ? m->bgraph_ready : (long_ctx ? m->graph_long_ready : m->graph_ready)) = true;
-    m->graph_stream = st;
-    return LA_OK;
+    const int reps = g_la_graph_reps > 1 ? g_la_graph_reps : 1;
+    return graph_capture(m->sgraphs[long_ctx], st, [&]() {
+        int rc = LA_OK;
+        for (int r = 0; r < reps && rc == LA_OK; ++r) {
+            form.zc_out = r + 1 == reps ? zc_out : nullptr;
+            rc = enqueue_step(m, st, nullptr, form);
+        }
+        return rc;
+    });
 }
 
 static int bstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* host_out, bool eager) {
@@ -795,25 +871,12 @@ static int bstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     int v = 0, bsplit = m->nsplit;
     const int target = m->nsplit / active > 1 ? m->nsplit / active : 1;
     while (v < 3 && bsplit > target && bsplit % 2 == 0) { bsplit /= 2; ++v; }
-    if (m->pen_on) ++m->pen_launches;
-    if (m->samp_on) ++m->samp_launches;
-    if (m->lp_on) ++m->lp_launches;
-    if (eager) {
-        int rc = enqueue_step(m, st, nullptr, true, nullptr, nullptr, bsplit);
-        if (rc != LA_OK) return rc;
-    } else {
-        if (m->bready[v] && m->bepoch[v] != g_la_graph_epoch) {      // a capture-time knob changed (la_debug_set): capture again
-            (void)hipGraphExecDestroy(m->bgraphs[v]);
-            m->bgraphs[v] = nullptr; m->bready[v] = false;
-        }
-        if (!m->bready[v]) {
-            int rc = build_graph(m, st, true, nullptr, nullptr, bsplit);
-            if (rc != LA_OK) return rc;
-            m->bgraphs[v] = m->bgraph_exec; m->bgraph_exec = nullptr; m->bgraph_ready = false;
-            m->bready[v] = true; m->bepoch[v] = g_la_graph_epoch;
-        }
-        HIPCHK(hipGraphLaunch(m->bgraphs[v], st));
-    }
+    count_stages(m);
+    StepForm form;
+    form.batch = true; form.bsplit = bsplit;
+    auto enqueue = [&]() { return enqueue_step(m, st, nullptr, form); };
+    const int rc = eager ? enqueue() : graph_run(m->bgraphs[v], st, enqueue);
+    if (rc != LA_OK) return rc;
     if (host_out)
         HIPCHK(hipMemcpyAsync(host_out, m->bstate, LA_BST_DST * sizeof(int), hipMemcpyDeviceToHost, st));
     return LA_OK;
@@ -937,33 +1000,24 @@ static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = fals
     MbGemm h{}; h.wp = m->w.lm_head; h.xp = m->mb_xp; h.N = c.vocab; h.K = c.hidden; h.nblk = nblk; h.n_wg = c.balanced_wg[2]; h.ksplit = 1;
     h.logits = m->mb_logits; h.cand_val = m->mb_cand_val; h.cand_idx = m->mb_cand_idx;
     KCHK(lk_mb_gemm(st, 3, h));
-    PenArgs pa{};
-    if (m->pen_on) {
-        pa.kind = LA_PEN_MBLOCK; pa.vocab = c.vocab; pa.n_slots = m->n_slots; pa.nblk = nblk;
-        pa.logits = m->mb_logits; pa.bitmaps = m->pen_bits; pa.penalty = m->pen_val; pa.ids = m->mb_ids;
-        pa.rowmask = (const unsigned long long*)m->mb_rowmask; pa.state = m->mb_out; pa.meta = m->mb_meta; pa.out = m->mb_out + LA_MOUT_ARGMAX;
-    }
-    if (m->samp_on) {
-        SampArgs sa{};
-        sa.p = pa;
-        sa.p.kind = LA_PEN_MBLOCK; sa.p.vocab = c.vocab; sa.p.n_slots = m->n_slots; sa.p.nblk = nblk; sa.p.logits = m->mb_logits;
-        sa.p.rowmask = (const unsigned long long*)m->mb_rowmask; sa.p.ids = m->mb_ids; sa.p.meta = m->mb_meta; sa.p.out = m->mb_out + LA_MOUT_ARGMAX;
-        sa.pen = m->pen_on ? 1 : 0; sa.pos = m->mb_pos; sa.params = m->samp_par;
-        KCHK(lk_sample_rows(st, sa));
-    } else if (m->pen_on) {
-        KCHK(lk_pen_argmax(st, pa));
-    } else
-    KCHK(lk_mb_argmax(st, m->mb_cand_val, m->mb_cand_idx, lk_mb_cand_slots(lwg), nblk, m->mb_out + LA_MOUT_ARGMAX));
-    KCHK(lk_mb_accept_scan(st, m->mb_meta, m->mb_ids, m->mb_rowmask, (const uint64_t*)(m->mb_in + LA_MIN_XMASK), m->mb_out + LA_MOUT_ARGMAX, nblk, c.max_keys, c.kv_ring ? 1 : 0, m->bstate, m->mb_out));
-    if (m->pen_on) KCHK(lk_pen_update(st, pa));
-    if (m->lp_on) {
-        LpArgs la{};
-        la.p.kind = LA_PEN_MBLOCK; la.p.vocab = c.vocab; la.p.n_slots = m->n_slots; la.p.nblk = nblk; la.p.logits = m->mb_logits;
-        la.p.state = m->mb_out; la.p.meta = m->mb_meta; la.p.out = m->mb_out + LA_MOUT_ARGMAX;
-        la.pos = m->mb_pos; la.log = m->lp_log; la.stride = m->lp_stride;
-        KCHK(lk_logprob_rows(st, la));
-    }
+    const StepRows rows = step_rows(m, LA_PEN_MBLOCK, nblk);
+    bool own = false;
+    int rc = pick_rows(m, st, rows, &own);
+    if (rc != LA_OK) return rc;
+    if (own) KCHK(lk_mb_argmax(st, m->mb_cand_val, m->mb_cand_idx, lk_mb_cand_slots(lwg), nblk, rows.argmax));
+    KCHK(lk_mb_accept_scan(st, m->mb_meta, m->mb_ids, m->mb_rowmask, (const uint64_t*)(m->mb_in + LA_MIN_XMASK), rows.argmax, nblk, c.max_keys, c.kv_ring ? 1 : 0, m->bstate, m->mb_out));
+    rc = after_scan(m, st, rows);
+    if (rc != LA_OK) return rc;
     KCHK(lk_mb_kv_commit(st, m->mb_kfresh, m->mb_vfresh, m->kmain, m->vmain, m->mb_out, nblk, c.n_layers, c.n_kv_heads, m->total_keys));
+    return LA_OK;
+}
+
+// the pass over the input block already on the device (m->mb_in): eager or through its captured graph, then the result header
+static int mstep_launch(la_llama* m, hipStream_t st, int nblk, bool wide, bool eager, int32_t* host_out) {
+    auto enqueue = [&]() { return enqueue_mstep(m, st, nblk, wide); };
+    const int rc = eager ? enqueue() : graph_run(m->mgraphs[(wide ? LA_MB_MAX + 1 : 0) + nblk], st, enqueue);
+    if (rc != LA_OK) return rc;
+    if (host_out) HIPCHK(hipMemcpyAsync(host_out, m->mb_out, LA_MOUT_DST * sizeof(int), hipMemcpyDeviceToHost, st));
     return LA_OK;
 }
 
@@ -973,35 +1027,10 @@ static int mstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* hos
     if (!m->mb_max || nblk < 1 || nblk > m->mb_max) { la_set_error("mstep: block count outside cfg.max_blocks"); return LA_E_ARG; }
     bool wide = false;                                   // any wide-tree piece in this pass: the masked attention instantiation
     for (int b = 0; b < nblk; ++b) wide = wide || host_in[LA_MIN_BLK + 4 * b + 2] == LA_MODE_TREE_PIECE;
-    const int gi = (wide ? LA_MB_MAX + 1 : 0) + nblk;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(m->mb_in, host_in, LA_MIN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
-    if (m->pen_on) ++m->pen_launches;
-    if (m->samp_on) ++m->samp_launches;
-    if (m->lp_on) ++m->lp_launches;
-    if (eager) {
-        int rc = enqueue_mstep(m, st, nblk, wide);
-        if (rc != LA_OK) return rc;
-    } else {
-        if (m->mready[gi] && m->mepoch[gi] != g_la_graph_epoch) {
-            (void)hipGraphExecDestroy(m->mgraphs[gi]);
-            m->mgraphs[gi] = nullptr; m->mready[gi] = false;
-        }
-        if (!m->mready[gi]) {
-            hipGraph_t g = nullptr;
-            HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            int rc = enqueue_mstep(m, st, nblk, wide);
-            hipError_t e = hipStreamEndCapture(st, &g);
-            if (rc != LA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-            HIPCHK(e);
-            HIPCHK(hipGraphInstantiate(&m->mgraphs[gi], g, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(g);
-            m->mready[gi] = true; m->mepoch[gi] = g_la_graph_epoch;
-        }
-        HIPCHK(hipGraphLaunch(m->mgraphs[gi], st));
-    }
-    if (host_out) HIPCHK(hipMemcpyAsync(host_out, m->mb_out, LA_MOUT_DST * sizeof(int), hipMemcpyDeviceToHost, st));
-    return LA_OK;
+    count_stages(m);
+    return mstep_launch(m, st, nblk, wide, eager, host_out);
 }
 // Drafts from the device trie: the step input is assembled on the device (k_mb_fill_from_trie) from the trie kernel's outputs, then
 // the captured graph of `nblk` plain blocks runs — nothing crosses PCIe but the result header.
@@ -1012,28 +1041,8 @@ extern "C" int la_llama_mstep_trie(la_llama* m, void* stream, int nblk, const in
     for (int b = 0; b < nblk; ++b) if (slots[b] < 0 || slots[b] >= m->n_slots) return LA_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     KCHK(lk_mb_fill_from_trie(st, d_ids, d_rowmask, d_n, slots, limits, last_tok, nblk, m->mb_in));
-    if (m->pen_on) ++m->pen_launches;
-    if (m->samp_on) ++m->samp_launches;
-    if (m->lp_on) ++m->lp_launches;
-    const int gi = nblk;
-    if (m->mready[gi] && m->mepoch[gi] != g_la_graph_epoch) {
-        (void)hipGraphExecDestroy(m->mgraphs[gi]);
-        m->mgraphs[gi] = nullptr; m->mready[gi] = false;
-    }
-    if (!m->mready[gi]) {
-        hipGraph_t g = nullptr;
-        HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_mstep(m, st, nblk, false);
-        hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc != LA_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
-        HIPCHK(e);
-        HIPCHK(hipGraphInstantiate(&m->mgraphs[gi], g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        m->mready[gi] = true; m->mepoch[gi] = g_la_graph_epoch;
-    }
-    HIPCHK(hipGraphLaunch(m->mgraphs[gi], st));
-    if (host_out) HIPCHK(hipMemcpyAsync(host_out, m->mb_out, LA_MOUT_DST * sizeof(int), hipMemcpyDeviceToHost, st));
-    return LA_OK;
+    count_stages(m);
+    return mstep_launch(m, st, nblk, false, false, host_out);
 }
 
 extern "C" int la_llama_mstep(la_llama* m, void* stream, const int32_t* host_in, int32_t* host_out) {
@@ -1047,26 +1056,24 @@ extern "C" int la_llama_step(la_llama* m, void* stream, const int32_t* host_in, 
     if (!m || !host_in || !host_out) return LA_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     // other staging blocks, or a capture-time knob (la_debug_set keys 7 / 8) changed since the capture: capture again
-    if ((m->graph_ready || m->graph_long_ready) && (m->zc_in != host_in || m->zc_out != host_out || m->graph_epoch != g_la_graph_epoch)) {
-        if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
-        if (m->graph_long) (void)hipGraphExecDestroy(m->graph_long);
-        m->graph_exec = m->graph_long = nullptr;
-        m->graph_ready = m->graph_long_ready = false;
-    }
+    // (BOTH forms go: they were captured over the same blocks at the same epoch)
+    const StepGraph* have = m->sgraphs[0].exec ? &m->sgraphs[0] : m->sgraphs[1].exec ? &m->sgraphs[1] : nullptr;
+    if (have && (m->zc_in != host_in || m->zc_out != host_out || have->epoch != g_la_graph_epoch))
+        for (StepGraph& g : m->sgraphs) graph_drop(g);
     // two captured forms of the step: the tree attention as ONE launch while the K/V of the kv heads of an XCD fit its L2 (every
     // workgroup of a head streams the head's whole K/V, the sharers find it in L2), key splits + combine beyond (distinct bytes per
     // CU).  The caller's hint word picks; both are exact at any context.
     const bool long_ctx = host_in[LA_IN_NKEYS_HINT] + LA_TREE_MAX > m->attn_thr;
-    if (!(long_ctx ? m->graph_long_ready : m->graph_ready)) {
+    if (!m->sgraphs[long_ctx].exec) {
         hipPointerAttribute_t pa;
         if (hipPointerGetAttributes(&pa, host_in) != hipSuccess || hipPointerGetAttributes(&pa, host_out) != hipSuccess) {
             (void)hipGetLastError();
             la_set_error("la_llama_step: host_in / host_out must be pinned host memory (zero-copy step I/O)");
             return LA_E_ARG;
         }
-        int rc = build_graph(m, st, false, host_in, host_out, 0, long_ctx);
+        int rc = capture_single(m, st, host_in, host_out, long_ctx);
         if (rc != LA_OK) return rc;
-        m->zc_in = host_in; m->zc_out = host_out; m->graph_epoch = g_la_graph_epoch;
+        m->zc_in = host_in; m->zc_out = host_out;
         // the OTHER form too, now (first call = set-up / prefill time) rather than on the first step that crosses attn_thr: capture +
         // instantiate of the whole model is a multi-ms stall that would otherwise land inside a decode loop (and inside
         // la_lookahead_decode).  Only when the cache can reach the other side of the threshold at all.
@@ -1077,18 +1084,16 @@ extern "C" int la_llama_step(la_llama* m, void* stream, const int32_t* host_in, 
         const int dist_thr = host_in[LA_IN_NKEYS_HINT] + LA_TREE_MAX - m->attn_thr;
         const bool mid_sequence = host_in[LA_IN_NKEYS_HINT] > 0 && m->seq_expected > 0;
         const bool worth_it = !mid_sequence || (dist_thr > -2 * LA_TREE_MAX && dist_thr < 2 * LA_TREE_MAX);
-        if (other_reachable && worth_it && !(long_ctx ? m->graph_ready : m->graph_long_ready)) {
-            if (build_graph(m, st, false, host_in, host_out, 0, !long_ctx) != LA_OK) {
+        if (other_reachable && worth_it && !m->sgraphs[!long_ctx].exec) {
+            if (capture_single(m, st, host_in, host_out, !long_ctx) != LA_OK) {
                 (void)hipGetLastError();                 // clear the sticky error of the failed capture; the required graph is ready
                 la_set_error("");
             }
         }
     }
     m->seq_expected += 1;
-    if (m->pen_on) ++m->pen_launches;
-    if (m->samp_on) ++m->samp_launches;
-    if (m->lp_on) ++m->lp_launches;
-    HIPCHK(hipGraphLaunch(long_ctx ? m->graph_long : m->graph_exec, st));
+    count_stages(m);
+    HIPCHK(hipGraphLaunch(m->sgraphs[long_ctx].exec, st));
     return LA_OK;
 }
 
@@ -1114,10 +1119,10 @@ extern "C" int la_llama_step_eager(la_llama* m, void* stream, const int32_t* hos
     if (!m || !host_in) return LA_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemcpyAsync(m->in, host_in, LA_IN_WORDS * sizeof(int), hipMemcpyHostToDevice, st));
-    if (m->pen_on) ++m->pen_launches;
-    if (m->samp_on) ++m->samp_launches;
-    if (m->lp_on) ++m->lp_launches;
-    int rc = enqueue_step(m, st, nullptr, false, nullptr, nullptr, 0, host_in[LA_IN_NKEYS_HINT] + LA_TREE_MAX > m->attn_thr);
+    count_stages(m);
+    StepForm form;
+    form.long_ctx = host_in[LA_IN_NKEYS_HINT] + LA_TREE_MAX > m->attn_thr;
+    int rc = enqueue_step(m, st, nullptr, form);
     if (rc != LA_OK) return rc;
     if (host_out)
         HIPCHK(hipMemcpyAsync(host_out, m->state, (LA_ST_OUTTOK + 64) * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1305,17 +1310,7 @@ extern "C" int la_llama_set_nkeys(la_llama* m, void* stream, int slot, int nkeys
 }
 
 // ---- repetition penalty on the device (la_penalty.hip) -----------------------------------------------------------------
-// every captured graph of the model holds the step WITH or WITHOUT the penalty stage: switching it on / off drops them (the next
-// step captures again, as after a g_la_graph_epoch change); a new value only rewrites the device word the stage reads
-static void drop_graphs(la_llama* m) {
-    if (m->graph_exec) (void)hipGraphExecDestroy(m->graph_exec);
-    if (m->graph_long) (void)hipGraphExecDestroy(m->graph_long);
-    m->graph_exec = m->graph_long = nullptr;
-    m->graph_ready = m->graph_long_ready = false;
-    for (int i = 0; i < 4; ++i) if (m->bready[i]) { (void)hipGraphExecDestroy(m->bgraphs[i]); m->bgraphs[i] = nullptr; m->bready[i] = false; }
-    for (int i = 0; i < 2 * (LA_MB_MAX + 1); ++i) if (m->mready[i]) { (void)hipGraphExecDestroy(m->mgraphs[i]); m->mgraphs[i] = nullptr; m->mready[i] = false; }
-}
-
+// switching the stage on / off drops the captured graphs (drop_graphs); a new value only rewrites the device word the stage reads
 extern "C" int la_llama_set_repetition_penalty(la_llama* m, void* stream, float penalty) {
     if (!m || !(penalty > 0.f) || !(penalty <= 3.0e38f)) { la_set_error("repetition penalty must be a finite float > 0 (1.0 = off)"); return LA_E_ARG; }
     const bool on = penalty != 1.0f;
@@ -1496,9 +1491,10 @@ extern "C" int la_llama_profile(la_llama* m, void* stream, const int32_t* host_i
     for (int it = 0; it < iters; ++it) {
         pf.used = 0; pf.cls.clear();
         HIPCHK(hipMemcpyAsync(m->state, saved, sizeof(saved), hipMemcpyHostToDevice, st));
-        int rc = enqueue_step(m, st, &pf);
+        int rc = enqueue_step(m, st, &pf, StepForm{});
         if (rc != LA_OK) return rc;
-        if (m->lp_on) ++m->lp_launches;                     // (a profiled step launches the stage like any other)
+        // not count_stages: a profiled step has always counted its log-probability launch only, and tests pin the three counters
+        if (m->lp_on) ++m->lp_launches;
         HIPCHK(hipStreamSynchronize(st));
         for (size_t i = 0; i + 1 < pf.used; ++i) {
             float ms = 0;

@@ -180,6 +180,7 @@ enum { LA_SAMP_SEED_LO = 0, LA_SAMP_SEED_HI = 1, LA_SAMP_TEMP = 2, LA_SAMP_TOPK 
        LA_SAMP_WORDS = 8 + 64 };     // the device parameter block (32-bit words; one stream word per slot from LA_SAMP_STREAM on)
 struct SampArgs {
     PenArgs p;                        // row addressing (kind, state, in, meta), logits, out; bitmaps / penalty / ids / rowmask when `pen`
+                                      // (the engine's steps fill all of p whatever `pen` is; the stage reads the four under `pen` only)
     int pen;                          // 1: apply the repetition penalty to the context members first (p.bitmaps, p.penalty)
     const int* pos;                   // RoPE position of every row (same index as the logits row)
     const unsigned* params;           // device parameter block (LA_SAMP_*), or null: the values below (unit entry)
@@ -196,7 +197,8 @@ int lk_sample_bits(hipStream_t st, unsigned seed_lo, unsigned seed_hi, unsigned 
 // launched after the accept scan; stored at log[slot][pos[row] + 1] (the position of the token being chosen)
 struct LpArgs {
     PenArgs p;                        // row addressing (kind, state, in, meta, nblk), logits; p.out = the ARGMAX words (read only);
-                                      // p.state is also where the scan left its keep plan (LA_ST_SRCIDX / LA_BST_DST / LA_MOUT_DST)
+                                      // p.state is also where the scan left its keep plan (LA_ST_SRCIDX / LA_BST_DST / LA_MOUT_DST);
+                                      // p.rowmask / ids / bitmaps / penalty are null: the stage reads no path and no context set
     const int* pos;                   // RoPE position of every row (same index as the logits row)
     float* log;                       // [n_slots][stride], or null (unit entry): out[row] instead
     int stride;
