@@ -56,23 +56,29 @@ __global__ __launch_bounds__(512) void k_tree_attn1(const bf16_t* __restrict__ q
                                                      int sl_ring, Attn1Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds1[];      // [Q fragments: 8 KiB][merge buffer]
     if constexpr (RIDE) { if ((int)blockIdx.x >= a.n_main) { attn1_rider(a.pf, (int)blockIdx.x - a.n_main); return; } }
-    const int nh = nh_nkv >> 16, nkv = nh_nkv & 0xffff, G = nh / nkv;
-    const int SL = sl_ring & 63, ring_tiles = sl_ring >> 8;
-    const int W = 32 / SL;                                            // token rows this workgroup stores
+    // The block decomposition without a division (it stands in front of the early K tile): a block id is
+    // ((kv head * G + head of the group) * 2 + token block) * SL + slice) * DV + dv, and SL, DV are powers of two, so everything below
+    // the head is shifts and masks; G = nh / nkv comes as log2 G in bits 3..6 of sl_ring (15: not a power of two — the one division
+    // left, taken by e.g. 28 heads over 4 kv heads).  nh_nkv carries G, not nh, in its upper half (the launcher's division).
+    const int nkv = nh_nkv & 0xffff, G = nh_nkv >> 16;
+    const int SL = sl_ring & 7, lsl = SL >> 1, lg = (sl_ring >> 3) & 15, lw = 5 - lsl, ring_tiles = sl_ring >> 8;
+    const int W = 1 << lw;                                            // token rows this workgroup stores: 32 / SL
+    static_assert(DV == 1 || DV == 2 || DV == 4, "DV is a shift");
     constexpr int NDB = 4 / DV, NV = 2 * NDB, NQ = 4 * NDB;           // this workgroup's 32-dim blocks of V, their fragments per tile, its head-dim groups of 4 per token
-    const int NS = G * 2 * SL * DV;                                   // workgroups that read the same kv head
-    const int b = blockIdx.x;
-    int hk, r;
-    if ((nkv & 7) == 0) { const int x = b & 7, q = b >> 3; hk = x * (nkv >> 3) + q / NS; r = q % NS; }     // sharers on one XCD
-    else { hk = b / NS; r = b % NS; }
-    const int dv = r % DV;                                            // owns the 32-dim blocks dv * NDB .. + NDB - 1
-    r /= DV;
-    const int tb = (r / SL) & 1, sl = r % SL;
-    const int h = hk * G + r / (2 * SL);
+    constexpr int LDV = DV >> 1;                                      // log2 DV
+    const unsigned b = blockIdx.x;
+    const int sh = 1 + lsl + LDV;                                     // 2 * SL * DV workgroups per head; G times that read the same kv head
+    const bool xcd = (nkv & 7) == 0;                                  // sharers on one XCD
+    const unsigned q = xcd ? b >> 3 : b, t = q >> sh;                 // t = (kv head [of this XCD]) * G + head of the group
+    const unsigned qn = lg == 15 ? t / (unsigned)G : t >> lg;
+    const int hk = xcd ? (int)((b & 7u) * (unsigned)(nkv >> 3) + qn) : (int)qn;
+    const int h = hk * G + (int)(t - qn * (unsigned)G);
+    const int dv = (int)(q & (unsigned)(DV - 1));                     // owns the 32-dim blocks dv * NDB .. + NDB - 1
+    const int sl = (int)(q >> LDV) & (SL - 1), tb = (int)(q >> (LDV + lsl)) & 1;
     const int lane = threadIdx.x & 63;
     const int par = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int hh = lane >> 5;
-    long long* const stamp = a.dbg_times ? a.dbg_times + ((size_t)b * 8 + par) * 8 : nullptr;
+    long long* const stamp = (kLaLab && a.dbg_times) ? a.dbg_times + ((size_t)b * 8 + par) * 8 : nullptr;
     if (stamp && lane == 0) stamp[0] = wall_clock64();
 
     const int KB = max_keys >> 5;
@@ -213,7 +219,8 @@ __global__ __launch_bounds__(512) void k_tree_attn1(const bf16_t* __restrict__ q
         ps += __shfl_xor(ps, 32, 64);
         l = l * alpha + ps;
         m = mn;
-        if (stamp && lane == 0 && stamp[5] == 0) stamp[5] = wall_clock64();      // first tile: scores done, V not yet awaited
+        if constexpr (kLaLab) { if (stamp && lane == 0 && stamp[5] == 0) stamp[5] = wall_clock64(); }      // first tile: scores done, V not yet awaited
+        else __builtin_amdgcn_sched_barrier(0);       // the product build keeps the scheduling boundary the (never taken) stamp branch was: without it the PV operands are hoisted over the softmax and spill
         if (__ballot(alpha != 1.0f) != 0ull) {          // a running maximum moved for some row: rescale (x * 1.0f is exact, so skipping is too)
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
@@ -296,7 +303,8 @@ __global__ __launch_bounds__(512) void k_tree_attn1(const bf16_t* __restrict__ q
             for (int s = 0; s < 8; ++s) kB[s] = kt[s * 64 + lane];
         }
         tile(it, kA, &vE);
-        if (stamp && lane == 0) stamp[2] = wall_clock64();
+        if constexpr (kLaLab) { if (stamp && lane == 0) stamp[2] = wall_clock64(); }
+        else __builtin_amdgcn_sched_barrier(0);
         it = nx;
         for (int k = 1; k < cnt; k += 2) {
             if (k + 1 < cnt) {
@@ -328,8 +336,9 @@ __global__ __launch_bounds__(512) void k_tree_attn1(const bf16_t* __restrict__ q
     float* const ml = lds1 + 2048 + 8 * NQ * 2 * W * 4;               // [par][W] {m, l}
     {
         const int col = lane & 31;
-        if (col / W == sl) {
-            const int j = (col % W) + W * hh;
+        if ((col >> lw) == sl) {
+            const int cw = col & (W - 1);
+            const int j = cw + W * hh;
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -337,13 +346,13 @@ __global__ __launch_bounds__(512) void k_tree_attn1(const bf16_t* __restrict__ q
                     const f32x4 v = {o[db][4 * i4], o[db][4 * i4 + 1], o[db][4 * i4 + 2], o[db][4 * i4 + 3]};
                     mg4[((par * NQ) + db * 4 + i4) * (2 * W) + j] = v;
                 }
-            if (hh == 0) { ml[(par * W + col % W) * 2] = m; ml[(par * W + col % W) * 2 + 1] = l; }
+            if (hh == 0) { ml[(par * W + cw) * 2] = m; ml[(par * W + cw) * 2 + 1] = l; }
         }
     }
     __syncthreads();
     for (int item = threadIdx.x; item < NQ * 2 * W; item += 512) {
-        const int jj = item % (2 * W), ql = item / (2 * W), q16 = dv * NQ + ql;      // q16: the head-dim group of 4 within the head
-        const int tl = jj % W, h2 = jj / W;
+        const int jj = item & (2 * W - 1), ql = item >> (lw + 1), q16 = dv * NQ + ql;      // q16: the head-dim group of 4 within the head
+        const int tl = jj & (W - 1), h2 = jj >> lw;
         float wp[8];
         float M = LA_NEG, L = 0.f;
 #pragma unroll
@@ -445,10 +454,15 @@ int lk_tree_attn1(hipStream_t st, const void* qf, const void* kmain, const void*
     a.qk = la_qk_scale(head_dim);
     const size_t lds = 8192 + (size_t)8 * (16 / DV) * 2 * W * 16 + (size_t)8 * W * 8;
     a.n_main = nh * 2 * SL * DV;
+    // the kernel's block decomposition: SL and DV are shifts (SL checked above, DV by the instantiation), and so is G = nh / nkv where it
+    // is a power of two (lg = 15: the kernel divides)
+    const int G = nh / nkv;
+    int lg = 15;
+    for (int i = 0; i < 15; ++i) if (G == (1 << i)) lg = i;
     int riders = 0;
     if (ride) { a.pf = *pf; riders = pf->n_consumers; }
 #define ATTN1_LAUNCH(RIDE, DV_, NKB_) k_tree_attn1<RIDE, DV_, NKB_><<<a.n_main + riders, 512, lds, st>>>((const bf16_t*)qf, (const unsigned long long*)rowmask, state, (const bf16_t*)kmain, \
-                                                (const bf16_t*)vmain, max_keys, (nh << 16) | nkv, window, SL | ((g_la_attn1_var & 1) << 7) | ((ring_keys >> 5) << 8), a)
+                                                (const bf16_t*)vmain, max_keys, (G << 16) | nkv, window, SL | (lg << 3) | ((g_la_attn1_var & 1) << 7) | ((ring_keys >> 5) << 8), a)
     if (DV == 1) {
         if (riders) ATTN1_LAUNCH(true, 1, 0);
         else ATTN1_LAUNCH(false, 1, 0);

@@ -135,6 +135,29 @@ __device__ __forceinline__ float attn_scale(float s, float qk) {
     else return bfr(bfr(s) * qk);
 }
 
+// Division by a launch constant without a division: floor(n / d) as ONE multiply-high.  magic = ceil(2^31 / d); with
+// e = magic * d - 2^31 (0 <= e < d),  n * magic / 2^31 = n / d + n * e / (d * 2^31), and the second term cannot carry the floor over the
+// next integer while n * e < 2^31 — so the result is exact for every n <= nmax whenever nmax * d < 2^31 (2 n < 2^32 then, too).
+// la_div_magic returns 0 where it cannot promise that; la_div_by_magic then divides.
+__host__ __device__ __forceinline__ unsigned la_div_magic(long long nmax, long long d) {
+    if (nmax < 0 || d < 1 || nmax * d >= (1ll << 31)) return 0u;
+    return (unsigned)(((1ull << 31) + (unsigned long long)d - 1ull) / (unsigned long long)d);
+}
+__host__ __device__ __forceinline__ unsigned la_div_by_magic(unsigned n, unsigned d, unsigned magic) {
+    if (__builtin_expect(magic == 0u, 0)) return n / d;
+    return (unsigned)(((unsigned long long)(n << 1) * magic) >> 32);
+}
+// K range of split ks of a slab launch: floor(K16 * ks / ksplit), 0 <= ks <= ksplit, so n <= K16 * ksplit: exact whenever
+// K16 * ksplit * ksplit < 2^31 — every 1 <= K16 <= 4096 at 1 <= ksplit <= 8 is far inside (tests/test_krange_magic.py runs that
+// whole domain against the division).  Where the launcher's magic is 0, the bound is the division every launch made before.
+__host__ __device__ __forceinline__ unsigned la_krange_magic(int K16, int ksplit) {
+    return (K16 < 1 || ksplit < 1) ? 0u : la_div_magic((long long)K16 * ksplit, ksplit);
+}
+__host__ __device__ __forceinline__ int la_krange_bound(int K16, int ks, int ksplit, unsigned magic) {
+    if (__builtin_expect(magic == 0u, 0)) return (int)(((long)K16 * ks) / ksplit);
+    return (int)la_div_by_magic((unsigned)(K16 * ks), (unsigned)ksplit, magic);
+}
+
 // accumulator register r of a 32x32 MFMA tile -> row inside the tile (col = lane&31)
 __device__ __forceinline__ int mfma_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 

@@ -383,6 +383,8 @@ struct GemmArgs {
     const bf16_t* wp;
     const bf16_t* xp;
     int K16;             // K / 16
+    unsigned kmagic;     // la_krange_magic(K16, ksplit) (la_common.h): the K range of a split without a division; 0 = divide
+    int ksplit;          // K splits of the launch (== gridDim.y)
     int N;               // output features (for SWIGLU: ffn, the packed matrix has 2*ffn rows)
     float* slabs;        // EPI_SLAB: [ksplit][64][N] fp32
     bf16_t* act_xp;      // EPI_SWIGLU: packed [64][N]
@@ -442,30 +444,39 @@ __device__ __forceinline__ void wave_krange(int t0, int twg, int wave, int kskew
 // (image bases, K, the expert switch) is therefore passed as leading scalars — the same values as the struct fields, which the
 // launchers keep filling — so that no s_load round trip stands between dispatch and the first HBM request (measured on the
 // single-wave kernels of the step: -0.2 us per launch).  kfl = ex_on | kskew << 1 | prio_hi << 8.
+// The leading scalars today (16 user SGPRs less the kernel-argument pointer: 14 dwords arrive preloaded):
+//   k_gemm64 / k_gemm64_w8   wp, xp, route_col, K16, kfl, kmagic, ksplit [, wsc]        (10 / 12 dwords)
+//   k_gemm64r / k_gemm64r_w8 wp, xp, route_col, K16, kfl, wg_chunks, nvl_pk, boff0..3   (14 dwords)
+// kmagic / ksplit: the K range of a split is la_krange_bound (la_common.h) — one multiply-high, no division; ksplit rides along
+// because gridDim.y would be a load from the hidden arguments.  Nothing else may stand between entry and the first weight request:
+//   * the measurement aids (stamps, dbg_noepi, kskew, prio_hi) are `if constexpr (kLaLab)` (la_knobs.h): no code in the product build;
+//   * the merged-expert addressing is the EX instantiation (lk_*_ex): every other launch never reads ex_w / ex_x / ex_act / ex_slab;
+//   * epilogue operands are read from the struct where the epilogue uses them (the compiler may request them early; nothing waits
+//     for them before the tile-sets are in flight — scripts/prologue_census.py, profiles/prologue_census.txt).
 // HW = true: the x operand is produced by OTHER workgroups of the same launch (role-fused launches, k_gateup_down): the first
 // weight tile-sets are requested, then the wave waits for ho_counter == ho_target (handover_wait), then loads x.
 struct BlockPos { int bx, by, bz, gx, gy; };
 // W8 = true: the image holds fp8 (e4m3fn) weights in the same fragment order with 1-byte elements (WP8, la_common.h) and wsc its
 // per-row fp32 scales; the loop streams the same k-tiles in the same MFMA order, converting each fragment in registers.
-template <int RB, int EPI, int D, int NW, bool HW = false, bool W8 = false>
+template <int RB, int EPI, int D, int NW, bool HW = false, bool W8 = false, bool EX = false>
 __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, const bf16_t* xp_s,
-                                            const float* __restrict__ route_col_s, int K16_s, int kfl, const GemmArgs& a,
+                                            const float* __restrict__ route_col_s, int K16_s, int kfl, unsigned kmagic_s, int ksplit_s, const GemmArgs& a,
                                             const BlockPos bp, float* red_, int* ho_counter, int ho_target,
                                             const float* __restrict__ wsc = nullptr) {
     float (*red)[RB * 2 * 16 * 64] = (float (*)[RB * 2 * 16 * 64])red_;
-    const int ex = (kfl & 1) ? bp.bz : 0;
+    const int ex = EX ? bp.bz : 0;
     if (expert_unused(route_col_s ? route_col_s + ex : nullptr)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nb0 = bp.bx * RB;
-    const int ksplit = bp.gy, ks = bp.by;
-    long long* const stamp = a.dbg_times ? a.dbg_times + ((size_t)(bp.by * bp.gx + bp.bx) * NW + wave) * 8 : nullptr;
+    const int ksplit = ksplit_s, ks = bp.by;            // ksplit_s == gridDim.y, which would be a load from the hidden arguments
+    long long* const stamp = (kLaLab && a.dbg_times) ? a.dbg_times + ((size_t)(bp.by * bp.gx + bp.bx) * NW + wave) * 8 : nullptr;
     if (stamp && lane == 0) { stamp[0] = wall_clock64(); stamp[4] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)); }
-    const int t0 = (int)(((long)K16_s * ks) / ksplit);
-    const int t1 = (int)(((long)K16_s * (ks + 1)) / ksplit);
+    const int t0 = la_krange_bound(K16_s, ks, ksplit, kmagic_s);
+    const int t1 = la_krange_bound(K16_s, ks + 1, ksplit, kmagic_s);
     // this wave's contiguous k-tile range
     int wb, cnt;
-    const int kskew = (kfl >> 1) & 127, prio_hi = kfl >> 8;
+    const int kskew = kLaLab ? (kfl >> 1) & 127 : 0, prio_hi = kLaLab ? kfl >> 8 : 0;
     wave_krange<NW>(t0, t1 - t0, wave, kskew, wb, cnt);
     if (NW == 8 && prio_hi > 0 && wave >= 4) { if (prio_hi == 1) __builtin_amdgcn_s_setprio(1); else if (prio_hi == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
     const int ngroups = (cnt + D - 1) / D;            // groups of D tiles; the last one may be partial
@@ -474,10 +485,13 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
     // integer offsets from the kernel-argument bases (not mutated pointers) keep the loads in the global
     // address space: a loop-carried pointer degrades to flat_load, which ties vmcnt and lgkmcnt together
     typedef typename std::conditional<W8, u32x2, bf16x8>::type wfrag_t;   // one lane's fragment of a k-tile: 8 or 16 bytes
-    const wfrag_t* __restrict__ wbase = (const wfrag_t*)(wp_s + ((kfl & 1) ? (size_t)ex * a.ex_w : (size_t)0));
+    const bf16_t* wp_e = wp_s;
+    const bf16_t* xp_e = xp_s;
+    if constexpr (EX) { wp_e += (size_t)ex * a.ex_w; xp_e += (size_t)ex * a.ex_x; }
+    const wfrag_t* __restrict__ wbase = (const wfrag_t*)wp_e;
     typedef const bf16x8* __restrict__ xptr_r;
     typedef const bf16x8* xptr_n;                                       // HW: written by other workgroups of this launch
-    typename std::conditional<HW, xptr_n, xptr_r>::type xbase = (const bf16x8*)(xp_s + ((kfl & 1) ? (size_t)ex * a.ex_x : (size_t)0));
+    typename std::conditional<HW, xptr_n, xptr_r>::type xbase = (const bf16x8*)xp_e;
     unsigned woff[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) woff[rb] = (unsigned)(((nb0 + rb) * K16_s + wb) * 64 + lane);
@@ -561,7 +575,7 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
     //      row-blocks — the epilogue runs on all waves instead of serialising on wave 0.  The buffer is laid out in
     //      16-byte units [wave][rb][tb][i/4][lane] so that both sides use ds_write_b128 / ds_read_b128.
     if (stamp && lane == 0) stamp[1] = wall_clock64();
-    if (a.dbg_noepi) return;
+    if (kLaLab && a.dbg_noepi) return;
     f32x4* red4 = (f32x4*)&red[0][0];
     {
 #pragma unroll
@@ -618,7 +632,7 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
     }
     const int tok = tb * 32 + tl;
     if constexpr (EPI == EPI_SLAB) {
-        float* o = a.slabs + (size_t)ex * a.ex_slab + (size_t)ks * LA_TB * a.N;
+        float* o = a.slabs + (EX ? (size_t)ex * a.ex_slab : (size_t)0) + (size_t)ks * LA_TB * a.N;
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -650,7 +664,7 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
                 pk[j] = (short)f2bf(sv * uv);
             }
             const int f = jb * 32 + 8 * (g0 + gg) + 4 * hh;    // 4 consecutive features f..f+3
-            *(bf16x4*)(a.act_xp + (size_t)ex * a.ex_act + xp_offset(tok, f)) = pk;
+            *(bf16x4*)(a.act_xp + (EX ? (size_t)ex * a.ex_act : (size_t)0) + xp_offset(tok, f)) = pk;
         }
     } else if constexpr (EPI == EPI_QKV) {
         // Workgroup b owns head slot b>>1, half u=b&1: row-block 0 = dims 32u+[0,32), row-block 1 = the RoPE
@@ -717,21 +731,23 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
     if (stamp && lane == 0) stamp[2] = wall_clock64();
 }
 
-template <int RB, int EPI, int D, int NW>
+// EX = true: the merged-expert launch (lk_*_ex): blockIdx.z enumerates the experts and the expert strides of `a` are read; every other
+// launch is an instantiation that never touches them
+template <int RB, int EPI, int D, int NW, bool EX = false>
 __global__ __launch_bounds__(NW * 64) void k_gemm64(const bf16_t* __restrict__ wp_s, const bf16_t* __restrict__ xp_s,
-                                                     const float* __restrict__ route_col_s, int K16_s, int kfl, GemmArgs a) {
+                                                     const float* __restrict__ route_col_s, int K16_s, int kfl, unsigned kmagic_s, int ksplit_s, GemmArgs a) {
     __shared__ __attribute__((aligned(16))) float red[NW][RB * 2 * 16 * 64];
     const BlockPos bp = {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y};
-    gemm64_body<RB, EPI, D, NW, false>(wp_s, xp_s, route_col_s, K16_s, kfl, a, bp, &red[0][0], nullptr, 0);
+    gemm64_body<RB, EPI, D, NW, false, false, EX>(wp_s, xp_s, route_col_s, K16_s, kfl, kmagic_s, ksplit_s, a, bp, &red[0][0], nullptr, 0);
 }
 // fp8 weights (WP8 image + per-row scales wsc): its own kernel, so that the 16-bit kernels keep their argument block and code
 template <int RB, int EPI, int D, int NW>
 __global__ __launch_bounds__(NW * 64) void k_gemm64_w8(const bf16_t* __restrict__ wp_s, const bf16_t* __restrict__ xp_s,
-                                                        const float* __restrict__ route_col_s, int K16_s, int kfl, GemmArgs a,
-                                                        const float* __restrict__ wsc) {
+                                                        const float* __restrict__ route_col_s, int K16_s, int kfl, unsigned kmagic_s, int ksplit_s,
+                                                        const float* __restrict__ wsc, GemmArgs a) {
     __shared__ __attribute__((aligned(16))) float red[NW][RB * 2 * 16 * 64];
     const BlockPos bp = {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y};
-    gemm64_body<RB, EPI, D, NW, false, true>(wp_s, xp_s, route_col_s, K16_s, kfl, a, bp, &red[0][0], nullptr, 0, wsc);
+    gemm64_body<RB, EPI, D, NW, false, true>(wp_s, xp_s, route_col_s, K16_s, kfl, kmagic_s, ksplit_s, a, bp, &red[0][0], nullptr, 0, wsc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -765,26 +781,28 @@ struct GemmRArgs {
 
 // Leading scalars = the prologue's operands (kernarg preload, see k_gemm64): nvl_pk = nvl[0..3] one byte each.
 // W8 = true: planned-8 image (la_common.h) + per-row fp32 scales wsc, as gemm64_body
-template <int RB, int EPI, int D, int NW, int NSF = 0, bool W8 = false>
+template <int RB, int EPI, int D, int NW, int NSF = 0, bool W8 = false, bool EX = false>
 __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, const bf16_t* xp_s,
                                              const float* __restrict__ route_col_s, int K16_s, int kfl, int wg_chunks_s,
                                              unsigned nvl_pk, int boff0, int boff1, int boff2, int boff3, const GemmRArgs& ra,
                                              const BlockPos bp, float* redr, const float* __restrict__ wsc = nullptr) {
     const GemmArgs& a = ra.g;
-    const int ex = (kfl & 1) ? bp.by : 0;
+    const int ex = EX ? bp.by : 0;
     if (expert_unused(route_col_s ? route_col_s + ex : nullptr)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    long long* const stamp = a.dbg_times ? a.dbg_times + ((size_t)(bp.by * bp.gx + bp.bx) * NW + wave) * 8 : nullptr;
+    long long* const stamp = (kLaLab && a.dbg_times) ? a.dbg_times + ((size_t)(bp.by * bp.gx + bp.bx) * NW + wave) * 8 : nullptr;
     if (stamp && lane == 0) { stamp[0] = wall_clock64(); stamp[4] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)); }
     int wb, cnt;
-    const int kskew = (kfl >> 1) & 127, prio_hi = kfl >> 8;
+    const int kskew = kLaLab ? (kfl >> 1) & 127 : 0, prio_hi = kLaLab ? kfl >> 8 : 0;
     wave_krange<NW>(0, K16_s, wave, kskew, wb, cnt);
     if (NW == 8 && prio_hi > 0 && wave >= 4) { if (prio_hi == 1) __builtin_amdgcn_s_setprio(1); else if (prio_hi == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3); }
     const int ngroups = (cnt + D - 1) / D;
     const int last_valid = cnt - (ngroups - 1) * D;
     typedef typename std::conditional<W8, u32x2, bf16x8>::type wfrag_t;   // one lane's fragment of a k-tile: 8 or 16 bytes
-    const wfrag_t* __restrict__ wbase = (const wfrag_t*)(wp_s + ((kfl & 1) ? (size_t)ex * a.ex_w : (size_t)0));
+    const bf16_t* wp_e = wp_s;
+    if constexpr (EX) wp_e += (size_t)ex * a.ex_w;
+    const wfrag_t* __restrict__ wbase = (const wfrag_t*)wp_e;
     typedef const bf16x8* __restrict__ xptr_r;
     typedef const bf16x8* xptr_n;                                       // fused producers write g.xp inside this kernel
     typename std::conditional<(NSF > 0), xptr_n, xptr_r>::type xbase = (const bf16x8*)xp_s;
@@ -895,7 +913,7 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
     }
 
     if (stamp && lane == 0) stamp[1] = wall_clock64();
-    if (a.dbg_noepi) return;
+    if (kLaLab && a.dbg_noepi) return;
     f32x4 pfv[8];
     const bool pf_on = EPI == EPI_SWIGLU && NSF == 0 && ra.pf.base != nullptr;        // wave-uniform
     if constexpr (EPI == EPI_SWIGLU && NSF == 0) {
@@ -1007,12 +1025,12 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                             const int feat = ra.R * bp.bx + 32 * qq + f;
                             const float gv = bfr(g4[j] * wsc[feat]), uv = bfr(u4[j] * wsc[a.N + feat]);
                             const float sv = bfr(gv / (1.0f + expf(-gv)));
-                            a.act_xp[(size_t)ex * a.ex_act + xp_offset(tok, feat)] = f2bf(sv * uv);
+                            a.act_xp[(EX ? (size_t)ex * a.ex_act : (size_t)0) + xp_offset(tok, feat)] = f2bf(sv * uv);
                         } else {
                             const float gv = bfr(g4[j]), uv = bfr(u4[j]);
                             const float sv = bfr(gv / (1.0f + expf(-gv)));
                             const int feat = ra.R * bp.bx + 32 * qq + f;
-                            a.act_xp[(size_t)ex * a.ex_act + xp_offset(tok, feat)] = f2bf(sv * uv);
+                            a.act_xp[(EX ? (size_t)ex * a.ex_act : (size_t)0) + xp_offset(tok, feat)] = f2bf(sv * uv);
                         }
                     }
                 }
@@ -1100,13 +1118,13 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
     if (stamp && lane == 0) stamp[2] = wall_clock64();
 }
 
-template <int RB, int EPI, int D, int NW, int NSF = 0>
+template <int RB, int EPI, int D, int NW, int NSF = 0, bool EX = false>
 __global__ __launch_bounds__(NW * 64) void k_gemm64r(const bf16_t* __restrict__ wp_s, const bf16_t* xp_s,
                                                       const float* __restrict__ route_col_s, int K16_s, int kfl, int wg_chunks_s,
                                                       unsigned nvl_pk, int boff0, int boff1, int boff2, int boff3, GemmRArgs ra) {
     extern __shared__ __attribute__((aligned(16))) float redr[];      // [NW][RB][16][64]
     const BlockPos bp = {(int)blockIdx.x, (int)blockIdx.y, 0, (int)gridDim.x, (int)gridDim.y};
-    gemm64r_body<RB, EPI, D, NW, NSF>(wp_s, xp_s, route_col_s, K16_s, kfl, wg_chunks_s, nvl_pk, boff0, boff1, boff2, boff3, ra, bp, redr);
+    gemm64r_body<RB, EPI, D, NW, NSF, false, EX>(wp_s, xp_s, route_col_s, K16_s, kfl, wg_chunks_s, nvl_pk, boff0, boff1, boff2, boff3, ra, bp, redr);
 }
 // fp8 weights (planned-8 image + per-row scales wsc)
 template <int RB, int EPI, int D, int NW>
@@ -1144,7 +1162,7 @@ __global__ __launch_bounds__(512) void k_gateup_down(const bf16_t* __restrict__ 
     } else {
         const int id = (int)blockIdx.x - n_gu;
         const BlockPos bp = {id % dn_gx, id / dn_gx, 0, dn_gx, dn_gy};
-        gemm64_body<RBD, EPI_SLAB, DD, 8, true>(dn.wp, dn.xp, nullptr, dn.K16, 0, dn, bp, lds_gd, counter, n_gu);
+        gemm64_body<RBD, EPI_SLAB, DD, 8, true>(dn.wp, dn.xp, nullptr, dn.K16, 0, dn.kmagic, dn_gy, dn, bp, lds_gd, counter, n_gu);
     }
 }
 
@@ -1983,8 +2001,9 @@ int g_la_graph_epoch = 0;     // bumped by la_debug_set when a capture-time knob
 
 #define LA_CAND_LDS (8 * LA_TB * 8)      // lm_head: [8 waves][64 tokens] (value, index) candidates behind the reduction buffer
 // leading scalar kernel arguments of the GEMM kernels (kernarg preload, see k_gemm64 / k_gemm64r)
-#define G64_HEAD(a) (a).wp, (a).xp, (a).route_col, (a).K16, (((a).ex_on ? 1 : 0) | (((a).kskew & 127) << 1) | ((a).prio_hi << 8))
-#define G64R_HEAD(ra) G64_HEAD((ra).g), (ra).wg_chunks, \
+#define G64_HEAD0(a) (a).wp, (a).xp, (a).route_col, (a).K16, (((a).ex_on ? 1 : 0) | (((a).kskew & 127) << 1) | ((a).prio_hi << 8))
+#define G64_HEAD(a) G64_HEAD0(a), (a).kmagic, (a).ksplit
+#define G64R_HEAD(ra) G64_HEAD0((ra).g), (ra).wg_chunks, \
     ((unsigned)(ra).nvl[0] | ((unsigned)(ra).nvl[1] << 8) | ((unsigned)(ra).nvl[2] << 16) | ((unsigned)(ra).nvl[3] << 24)), \
     (ra).boff[0], (ra).boff[1], (ra).boff[2], (ra).boff[3]
 #define LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -2038,12 +2057,12 @@ int lk_gemm64_slab(hipStream_t st, const void* wp, const void* xp, int N, int K,
                    const float* route_col, const float* wscale) {
     const int rb = rbv & 0xff, variant = rbv >> 8;
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = N; a.slabs = slabs;
-    a.route_col = route_col; a.slab_wt = g_la_slab_wt;
+    a.route_col = route_col; a.slab_wt = g_la_slab_wt; a.ksplit = ksplit; a.kmagic = la_krange_magic(a.K16, ksplit);
     if (wscale) {
         if (rb != 2 || (N % 64) || route_col) return -1;
         dim3 g(N / 64, ksplit);
-        if (variant == 3) k_gemm64_w8<2, EPI_SLAB, 12, 8><<<g, 512, 0, st>>>(G64_HEAD(a), a, wscale);       // o_proj
-        else if (variant == 0) k_gemm64_w8<2, EPI_SLAB, 16, 4><<<g, 256, 0, st>>>(G64_HEAD(a), a, wscale);  // down_proj
+        if (variant == 3) k_gemm64_w8<2, EPI_SLAB, 12, 8><<<g, 512, 0, st>>>(G64_HEAD(a), wscale, a);       // o_proj
+        else if (variant == 0) k_gemm64_w8<2, EPI_SLAB, 16, 4><<<g, 256, 0, st>>>(G64_HEAD(a), wscale, a);  // down_proj
         else return -1;
         LAUNCH_CHECK(); return 0;
     }
@@ -2053,10 +2072,10 @@ int lk_gemm64_slab(hipStream_t st, const void* wp, const void* xp, int N, int K,
 int lk_gemm64_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int K, void* act_xp, int variant,
                      const float* route_col, const float* wscale) {
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = F; a.act_xp = (bf16_t*)act_xp;
-    a.route_col = route_col;
+    a.route_col = route_col; a.ksplit = 1; a.kmagic = la_krange_magic(a.K16, 1);
     if (wscale) {
         if (variant != 0 || route_col) return -1;
-        k_gemm64_w8<2, EPI_SWIGLU, 16, 4><<<dim3(F / 32, 1), 256, 0, st>>>(G64_HEAD(a), a, wscale);
+        k_gemm64_w8<2, EPI_SWIGLU, 16, 4><<<dim3(F / 32, 1), 256, 0, st>>>(G64_HEAD(a), wscale, a);
         LAUNCH_CHECK(); return 0;
     }
     return launch_gemm<2, EPI_SWIGLU>(st, a, F / 32, 1, variant);
@@ -2065,7 +2084,7 @@ int lk_gemm64_logits(hipStream_t st, const void* wp, const void* xp, int V, int 
                      float* cv, int* ci) {
     const int rb = rbv & 0xff, variant = rbv >> 8;
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = V;
-    a.logits = (bf16_t*)logits; a.cand_val = cv; a.cand_idx = ci;
+    a.logits = (bf16_t*)logits; a.cand_val = cv; a.cand_idx = ci; a.ksplit = 1; a.kmagic = la_krange_magic(a.K16, 1);
     if (rb == 2 && (V % 64) == 0) return launch_gemm<2, EPI_LOGITS>(st, a, V / 64, 1, variant);
     return launch_gemm<1, EPI_LOGITS>(st, a, V / 32, 1, variant);
 }
@@ -2076,10 +2095,10 @@ int lk_gemm64_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int nk
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = (nh + 2 * nkv) * 128;
     a.pos = pos; a.rcos = (const bf16_t*)rcos; a.rsin = (const bf16_t*)rsin;
     a.qf = (bf16_t*)qf; a.kfresh = (bf16_t*)kfresh; a.vfresh = (bf16_t*)vfresh; a.nh = nh; a.nkv = nkv;
-    a.qkv_bias = (const bf16_t*)qkv_bias;
+    a.qkv_bias = (const bf16_t*)qkv_bias; a.ksplit = 1; a.kmagic = la_krange_magic(a.K16, 1);
     if (wscale) {
         if (variant != 0) return -1;
-        k_gemm64_w8<2, EPI_QKV, 16, 4><<<dim3(a.N / 64, 1), 256, 0, st>>>(G64_HEAD(a), a, wscale);
+        k_gemm64_w8<2, EPI_QKV, 16, 4><<<dim3(a.N / 64, 1), 256, 0, st>>>(G64_HEAD(a), wscale, a);
         LAUNCH_CHECK(); return 0;
     }
     return launch_gemm<2, EPI_QKV>(st, a, a.N / 64, 1, variant);
@@ -2247,7 +2266,7 @@ int lk_gateup_down(hipStream_t st, const void* wgu, const void* xp, int F, int K
     GemmRArgs ra{}; ra.g.kskew = 0; ra.g.wp = (const bf16_t*)wgu; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = F; ra.g.act_xp = (bf16_t*)act_xp;
     ra.R = F / n_wg; if (F % n_wg || ra.R > 64 || ra.R <= 32 || (N % 64) || (F % 16) || !counter) return -1;
     fill_nv(ra, ra.R, 2, 2);
-    GemmArgs d{}; d.wp = (const bf16_t*)wdown; d.xp = (const bf16_t*)act_xp; d.K16 = F / 16; d.N = N; d.slabs = slabs;
+    GemmArgs d{}; d.wp = (const bf16_t*)wdown; d.xp = (const bf16_t*)act_xp; d.K16 = F / 16; d.N = N; d.slabs = slabs; d.ksplit = ksplit; d.kmagic = la_krange_magic(d.K16, ksplit);
     const int gx = N / 64, n_dn = gx * ksplit;
     if (lk_gemm64r_init() != 0) return -1;
 #define GD(DD) k_gateup_down<2, DD><<<n_wg + n_dn, 512, 8 * 4 * 4096, st>>>(ra.g.wp, ra.g.xp, ra.g.K16, 0, ra.wg_chunks, \
@@ -2272,6 +2291,7 @@ int lk_gemm64r_init() {
     if (hipFuncSetAttribute((const void*)k_tree_attn<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             2 * LA_ATT_PAR * 66 * 64 * sizeof(float)) != hipSuccess) return -1;
     hipError_t e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_LOGITS, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096 + LA_CAND_LDS);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<2, EPI_QKV, 8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 2 * 4096);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
@@ -2491,25 +2511,26 @@ int lk_gemm64r_swiglu_ex(hipStream_t st, const void* wp0, long w_stride, const v
     ra.g.route_col = route_w; ra.g.ex_on = 1; ra.g.ex_w = w_stride; ra.g.ex_x = 0; ra.g.ex_act = act_stride;
     ra.R = F / n_wg; if (F % n_wg || ra.R > 64 || ra.R <= 32 || E < 1 || E > LA_MOE_MAX_E) return -1;
     fill_nv(ra, ra.R, 2, 2);
-    k_gemm64r<4, EPI_SWIGLU, 4, 8><<<dim3(n_wg, E), 512, 8 * 4 * 4096, st>>>(G64R_HEAD(ra), ra);
+    if (lk_gemm64r_init() != 0) return -1;
+    k_gemm64r<4, EPI_SWIGLU, 4, 8, 0, true><<<dim3(n_wg, E), 512, 8 * 4 * 4096, st>>>(G64R_HEAD(ra), ra);
     LAUNCH_CHECK(); return 0;
 }
 int lk_gemm64_swiglu_ex(hipStream_t st, const void* wp0, long w_stride, const void* xp, int F, int K, void* act0, long act_stride,
                         const float* route_w, int E) {
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp0; a.xp = (const bf16_t*)xp; a.K16 = K / 16; a.N = F; a.act_xp = (bf16_t*)act0;
-    a.route_col = route_w; a.ex_on = 1; a.ex_w = w_stride; a.ex_act = act_stride;
+    a.route_col = route_w; a.ex_on = 1; a.ex_w = w_stride; a.ex_act = act_stride; a.ksplit = 1; a.kmagic = la_krange_magic(a.K16, 1);
     if (E < 1 || E > LA_MOE_MAX_E) return -1;
-    k_gemm64<2, EPI_SWIGLU, 8, 4><<<dim3(F / 32, 1, E), 256, 0, st>>>(G64_HEAD(a), a);
+    k_gemm64<2, EPI_SWIGLU, 8, 4, true><<<dim3(F / 32, 1, E), 256, 0, st>>>(G64_HEAD(a), a);
     LAUNCH_CHECK(); return 0;
 }
 int lk_gemm64_slab_ex(hipStream_t st, const void* wp0, long w_stride, const void* xp0, long x_stride, int N, int K, int rbv, int ksplit,
                       float* slabs0, long slab_stride, const float* route_w, int E) {
     const int rb = rbv & 0xff;
     GemmArgs a{}; a.dbg_noepi = g_la_dbg_noepi; a.kskew = g_la_kskew; a.prio_hi = g_la_prio_hi; a.dbg_times = g_la_dbg_times; a.wp = (const bf16_t*)wp0; a.xp = (const bf16_t*)xp0; a.K16 = K / 16; a.N = N; a.slabs = slabs0;
-    a.route_col = route_w; a.ex_on = 1; a.ex_w = w_stride; a.ex_x = x_stride; a.ex_slab = slab_stride;
+    a.route_col = route_w; a.ex_on = 1; a.ex_w = w_stride; a.ex_x = x_stride; a.ex_slab = slab_stride; a.ksplit = ksplit; a.kmagic = la_krange_magic(a.K16, ksplit);
     if (E < 1 || E > LA_MOE_MAX_E) return -1;
-    if (rb == 2 && (N % 64) == 0) k_gemm64<2, EPI_SLAB, 8, 4><<<dim3(N / 64, ksplit, E), 256, 0, st>>>(G64_HEAD(a), a);
-    else k_gemm64<1, EPI_SLAB, 8, 4><<<dim3(N / 32, ksplit, E), 256, 0, st>>>(G64_HEAD(a), a);
+    if (rb == 2 && (N % 64) == 0) k_gemm64<2, EPI_SLAB, 8, 4, true><<<dim3(N / 64, ksplit, E), 256, 0, st>>>(G64_HEAD(a), a);
+    else k_gemm64<1, EPI_SLAB, 8, 4, true><<<dim3(N / 32, ksplit, E), 256, 0, st>>>(G64_HEAD(a), a);
     LAUNCH_CHECK(); return 0;
 }
 int lk_moe_accum_all(hipStream_t st, const float* slabs0, long slab_stride, int n_slabs, const float* route_w, int E, int hidden, void* acc) {

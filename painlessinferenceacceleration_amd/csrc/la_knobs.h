@@ -40,12 +40,16 @@
     X(g_la_fatx,             1,    36, 0, 1)       /* slab launches at 5-8 blocks (two token tiles per wave) with the x fragments streamed into MFMA operand registers (k_gemm_fat, STG = 2) */ \
     X(g_la_attn1_form,      20,    37, 0, 1143)    /* single-launch attention with V's head dims over DV workgroups: DV (2 | 4) | SL << 4 | ring tiles << 8 (0 | 2..4); 0 = (SL = 2, DV = 1) */
 
+// kLaLab: the kernels test it with `if constexpr`, so that in the product build the stamps, the timing probe and the K-skew / priority
+// handling are no code at all — not a test of a value that first had to be loaded from the kernel-argument block
 #if LA_LAB
+static constexpr bool kLaLab = true;
 #define LA_KNOB_DECL(name, dflt, key, lo, hi) extern int name;
 LA_KNOB_TABLE(LA_KNOB_DECL)
 extern int g_la_fork_pf[5];            // la_lab_set keys 26..30: forked weight-prefetch branch of the single-sequence graph (KiB per stage)
 extern long long* g_la_dbg_times;      // la_lab_set_ptr key 0: device buffer the GEMM / trie kernels stamp with wall_clock64()
 #else
+static constexpr bool kLaLab = false;
 #define LA_KNOB_DECL(name, dflt, key, lo, hi) static constexpr int name = dflt;
 LA_KNOB_TABLE(LA_KNOB_DECL)
 static constexpr int g_la_fork_pf[5] = {0, 0, 0, 0, 0};
