@@ -158,6 +158,17 @@ __host__ __device__ __forceinline__ int la_krange_bound(int K16, int ks, int ksp
     return (int)la_div_by_magic((unsigned)(K16 * ks), (unsigned)ksplit, magic);
 }
 
+// Row plan of one workgroup region of a planned image (la_pack_planned): `matrices` x `blocks_per_matrix` virtual 32-row blocks of which R rows
+// per matrix are valid.  nv = valid rows of each block, nvl = stored rows (nv rounded up to 4: a tile is a whole number of 128-B lines),
+// boff = 16-byte-chunk offset of each block inside the region; returns the chunks per region.  The 64-row and the multi-block launchers share it.
+inline int la_fill_plan(int* nv, int* nvl, int* boff, int R, int blocks_per_matrix, int matrices, int K16) {
+    for (int m = 0; m < matrices; ++m)
+        for (int b = 0; b < blocks_per_matrix; ++b) { int v = R - 32 * b; if (v > 32) v = 32; nv[m * blocks_per_matrix + b] = v; }
+    int off = 0;
+    for (int i = 0; i < matrices * blocks_per_matrix; ++i) { nvl[i] = (nv[i] + 3) & ~3; boff[i] = off; off += nvl[i] * 2 * K16; }
+    return off;
+}
+
 // accumulator register r of a 32x32 MFMA tile -> row inside the tile (col = lane&31)
 __device__ __forceinline__ int mfma_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 

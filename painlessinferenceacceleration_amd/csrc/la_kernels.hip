@@ -2113,18 +2113,15 @@ void lk_qkv_row_perm(int nh, int nkv, int* perm) {
     }
 }
 // ---- balanced variants (one workgroup per CU): weights packed from the row plan of lk_rowplan ----
+// what every balanced 64-row launch starts from: the lab's probe / skew / priority knobs (constexpr defaults in the product build), operands, K, N
+static GemmRArgs gemm64r_args(const void* wp, const void* xp, int K, int N) {
+    GemmRArgs ra{};
+    ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times;
+    ra.g.wp = (const bf16_t*)wp; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = N;
+    return ra;
+}
 static void fill_nv(GemmRArgs& ra, int R, int blocks_per_matrix, int matrices) {
-    for (int m = 0; m < matrices; ++m)
-        for (int b = 0; b < blocks_per_matrix; ++b) {
-            int v = R - 32 * b; if (v > 32) v = 32;
-            ra.nv[m * blocks_per_matrix + b] = v;
-        }
-    int off = 0;
-    for (int i = 0; i < matrices * blocks_per_matrix; ++i) {
-        ra.nvl[i] = (ra.nv[i] + 3) & ~3;
-        ra.boff[i] = off; off += ra.nvl[i] * 2 * ra.g.K16;
-    }
-    ra.wg_chunks = off;
+    ra.wg_chunks = la_fill_plan(ra.nv, ra.nvl, ra.boff, R, blocks_per_matrix, matrices, ra.g.K16);
 }
 // elements of the planned image (stored rows x K)
 long lk_planned_elems(int kind, int n_rows, int K, int n_wg) {
@@ -2202,7 +2199,7 @@ static bool set_fused_norm(GemmRArgs& ra, const FusedNorm* fn, int n_wg) {
 }
 int lk_gemm64r_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int K, int n_wg, void* act_xp,
                       const float* route_col, const FusedNorm* fn, const PfDesc* pf, const float* wscale) {
-    GemmRArgs ra{}; ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times; ra.g.wp = (const bf16_t*)wp; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = F; ra.g.act_xp = (bf16_t*)act_xp;
+    GemmRArgs ra = gemm64r_args(wp, xp, K, F); ra.g.act_xp = (bf16_t*)act_xp;
     ra.g.route_col = route_col;
     ra.R = F / n_wg; if (F % n_wg || ra.R > 64 || ra.R <= 32) return -1;
     fill_nv(ra, ra.R, 2, 2);
@@ -2226,7 +2223,7 @@ int lk_gemm64r_swiglu(hipStream_t st, const void* wp, const void* xp, int F, int
     LAUNCH_CHECK(); return 0;
 }
 int lk_gemm64r_logits(hipStream_t st, const void* wp, const void* xp, int V, int K, int n_wg, void* logits, float* cv, int* ci) {
-    GemmRArgs ra{}; ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times; ra.g.wp = (const bf16_t*)wp; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = V;
+    GemmRArgs ra = gemm64r_args(wp, xp, K, V);
     ra.g.logits = (bf16_t*)logits; ra.g.cand_val = cv; ra.g.cand_idx = ci;
     ra.R = V / n_wg; if (V % n_wg || ra.R > 128 || ra.R <= 96) return -1;
     fill_nv(ra, ra.R, 4, 1);
@@ -2237,7 +2234,7 @@ int lk_gemm64r_qkv(hipStream_t st, const void* wp, const void* xp, int nh, int n
                    const void* rcos, const void* rsin, void* qf, void* kfresh, void* vfresh, const FusedNorm* fn, const void* qkv_bias,
                    const float* wscale) {
     if (qkv_bias && g_la_dbg_noepi) return -1;          // the timing probe writes no epilogue: it would drop the bias
-    GemmRArgs ra{}; ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times; ra.g.wp = (const bf16_t*)wp; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = (nh + 2 * nkv) * 128;
+    GemmRArgs ra = gemm64r_args(wp, xp, K, (nh + 2 * nkv) * 128);
     ra.g.pos = pos; ra.g.rcos = (const bf16_t*)rcos; ra.g.rsin = (const bf16_t*)rsin;
     ra.g.qf = (bf16_t*)qf; ra.g.kfresh = (bf16_t*)kfresh; ra.g.vfresh = (bf16_t*)vfresh; ra.g.nh = nh; ra.g.nkv = nkv;
     ra.g.qkv_bias = (const bf16_t*)qkv_bias;
@@ -2290,19 +2287,25 @@ int lk_gemm64r_init() {
                             2 * LA_ATT_PAR * 66 * 64 * sizeof(float)) != hipSuccess) return -1;
     if (hipFuncSetAttribute((const void*)k_tree_attn<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             2 * LA_ATT_PAR * 66 * 64 * sizeof(float)) != hipSuccess) return -1;
-    hipError_t e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_LOGITS, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096 + LA_CAND_LDS);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<2, EPI_QKV, 8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 2 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<2, EPI_QKV, 8, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 2 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r<4, EPI_SWIGLU, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r_w8<4, EPI_SWIGLU, 6, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gemm64r_w8<2, EPI_QKV, 12, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 8 * 2 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gateup_down<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gateup_down<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gateup_down<2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gateup_down<2, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 4 * 4096);
+    // the balanced 64-row instantiations whose dynamic-LDS limit is raised: kernel, bytes
+    static const struct { const void* kernel; int lds; } rows[] = {
+        {(const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8>, 8 * 4 * 4096},
+        {(const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8, 0, true>, 8 * 4 * 4096},
+        {(const void*)k_gemm64r<4, EPI_LOGITS, 4, 8>, 8 * 4 * 4096 + LA_CAND_LDS},
+        {(const void*)k_gemm64r<2, EPI_QKV, 8, 8>, 2 * 8 * 2 * 4096},
+        {(const void*)k_gemm64r<4, EPI_SWIGLU, 4, 8, 4>, 8 * 4 * 4096},
+        {(const void*)k_gemm64r<2, EPI_QKV, 8, 8, 4>, 2 * 8 * 2 * 4096},
+        {(const void*)k_gemm64r<4, EPI_SWIGLU, 8, 4>, 4 * 4 * 4096},
+        {(const void*)k_gemm64r_w8<4, EPI_SWIGLU, 6, 8>, 8 * 4 * 4096},
+        {(const void*)k_gemm64r_w8<2, EPI_QKV, 12, 8>, 2 * 8 * 2 * 4096},
+        {(const void*)k_gateup_down<2, 4>, 8 * 4 * 4096},
+        {(const void*)k_gateup_down<2, 8>, 8 * 4 * 4096},
+        {(const void*)k_gateup_down<2, 4, 4>, 8 * 4 * 4096},
+        {(const void*)k_gateup_down<2, 8, 4>, 8 * 4 * 4096},
+    };
+    hipError_t e = hipSuccess;
+    for (const auto& r : rows)
+        if (e == hipSuccess) e = hipFuncSetAttribute(r.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds);
     if (e != hipSuccess) return (int)e;
     if (lk_attn1_init() != 0) return -1;
     g_attr_done = true;
@@ -2507,7 +2510,7 @@ static int tree_attn_launch(hipStream_t st, AttnArgs a, int n_slots, void* attn_
 // ---- merged MoE launches: E experts in one grid ----
 int lk_gemm64r_swiglu_ex(hipStream_t st, const void* wp0, long w_stride, const void* xp, int F, int K, int n_wg, void* act0,
                          long act_stride, const float* route_w, int E) {
-    GemmRArgs ra{}; ra.g.dbg_noepi = g_la_dbg_noepi; ra.g.kskew = g_la_kskew; ra.g.prio_hi = g_la_prio_hi; ra.g.dbg_times = g_la_dbg_times; ra.g.wp = (const bf16_t*)wp0; ra.g.xp = (const bf16_t*)xp; ra.g.K16 = K / 16; ra.g.N = F; ra.g.act_xp = (bf16_t*)act0;
+    GemmRArgs ra = gemm64r_args(wp0, xp, K, F); ra.g.act_xp = (bf16_t*)act0;
     ra.g.route_col = route_w; ra.g.ex_on = 1; ra.g.ex_w = w_stride; ra.g.ex_x = 0; ra.g.ex_act = act_stride;
     ra.R = F / n_wg; if (F % n_wg || ra.R > 64 || ra.R <= 32 || E < 1 || E > LA_MOE_MAX_E) return -1;
     fill_nv(ra, ra.R, 2, 2);

@@ -16,10 +16,9 @@
 #include "la_common.h"
 #include "la_mblock.h"
 #include "la_knobs.h"
+#include "la_mb_forms.h"      // MB_SLAB / MB_SWIGLU / MB_QKV / MB_LOGITS, the table of GEMM forms and its selector
 
 #define LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-enum { MB_SLAB = 0, MB_SWIGLU = 1, MB_QKV = 2, MB_LOGITS = 3 };
 
 // k-tile range [t0, t1) of K split ks.  An even K16 is cut on EVEN k-tiles (round 5): every multi-block GEMM family uses the same
 // boundaries (so their split-K slabs stay bit-identical to each other), and the fat-wave kernels, which consume whole 2-k-tile stages,
@@ -2607,92 +2606,32 @@ __global__ __launch_bounds__(256) void k_kv_commit_mb(const bf16_t* __restrict__
 // launchers
 // =============================================================================================================
 static bool g_mb_attr = false;
-template <int RBV, int TW, int EPI>
-static void wide_launch(dim3 grid, hipStream_t st, const MbArgs& a) {
-    // schedule (k_gemm_wide SCH): buffer-addressed pieces everywhere; a fragment read after every MFMA where a wave has >= 3 token tiles
-    // (6+ MFMAs per half stage to cover a read; with 1-2 tiles the reads-together form covers them better).  Mistral bs=8 9.88-9.97 ->
-    // 9.70-9.72 ms, 13B bs=4 10.68-10.73 -> 10.59-10.63 ms per step (profiles/r04_wide_gemm_schedule.txt); la_lab_set(24, 0) = schedule 0
-    constexpr int SCH = TW >= 3 ? 3 : 2;
-    if (g_la_mb_sch) k_gemm_wide<RBV, TW, EPI, 0, SCH><<<grid, 512, WideGeom<RBV, TW>::LDS, st>>>(a);
-    else k_gemm_wide<RBV, TW, EPI, 0, 0><<<grid, 512, WideGeom<RBV, TW>::LDS, st>>>(a);
-}
 template <typename K> static hipError_t set_lds(K k, int bytes) {
     return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
-static constexpr int mb_lds(int nt) { return (2 * 4 * nt * 1024) > 65536 ? (2 * 4 * nt * 1024) : 65536; }   // x double buffer vs reduction (64 KiB)
+
+// The multi-block GEMM forms of this build (la_mb_forms.h), one kernel per row of kMbForms: what lk_mb_init attributes and launch_mb launches.
+#define LA_MBK_MB(a, b, c, d, e, f, g)   k_gemm_mb<a, b, MB_##c, (d != 0), e>
+#define LA_MBK_WIDE(a, b, c, d, e, f, g) k_gemm_wide<a, b, MB_##c, d, e>
+#define LA_MBK_FAT(a, b, c, d, e, f, g)  k_gemm_fat<a, b, MB_##c, d, e, f, g>
+#define LA_MBK_FATD(a, b, c, d, e, f, g) k_gemm_fatd<a, b>
+#define LA_MBG_MB(a, b, f)   la_mb_lds_mb(b)
+#define LA_MBG_WIDE(a, b, f) WideGeom<a, b>::LDS
+#define LA_MBG_FAT(a, b, f)  FatGeom<a, b, f>::LDS
+#define LA_MBG_FATD(a, b, f) LA_FATD_LDS
+#define LA_MB_KERNEL(FAM, a, b, c, d, e, f, g) (const void*)LA_MBK_##FAM(a, b, c, d, e, f, g),
+static const void* const kMbKernels[MBF_COUNT] = { LA_MB_FORMS(LA_MB_KERNEL) };
+#define LA_MB_GEOM(FAM, a, b, c, d, e, f, g) \
+    static_assert(kMbForms[MBF_##FAM##_##a##_##b##_##c##_##d##_##e##_##f##_##g].lds == LA_MBG_##FAM(a, b, f), "LDS bytes of a form = its kernel's geometry");
+LA_MB_FORMS(LA_MB_GEOM)
+#undef LA_MB_GEOM
+#undef LA_MB_KERNEL
 
 int lk_mb_init() {
     if (g_mb_attr) return 0;
     hipError_t e = hipSuccess;
-#define SETALL(NT) \
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<2, NT, MB_SLAB>, mb_lds(NT)); \
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<4, NT, MB_SWIGLU>, mb_lds(NT)); \
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<2, NT, MB_QKV>, mb_lds(NT)); \
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<4, NT, MB_LOGITS>, mb_lds(NT));
-    SETALL(2) SETALL(4) SETALL(8)
-#undef SETALL
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<4, 4, MB_SLAB, true>, mb_lds(4));
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<8, 4, MB_SWIGLU, true>, mb_lds(4));
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<2, 4, MB_SLAB, true>, mb_lds(4));
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<4, 4, MB_SWIGLU, true>, mb_lds(4));
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<2, 4, MB_SLAB, true, 4>, mb_lds(4));
-    if (e == hipSuccess) e = set_lds(k_gemm_mb<4, 4, MB_SWIGLU, true, 4>, mb_lds(4));
-#define SETW4(T) \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<8, T, MB_SWIGLU>, WideGeom<8, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_SWIGLU>, WideGeom<4, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_LOGITS>, WideGeom<4, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<8, T, MB_SWIGLU, 0, (T >= 3 ? 3 : 2)>, WideGeom<8, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_SWIGLU, 0, (T >= 3 ? 3 : 2)>, WideGeom<4, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_LOGITS, 0, (T >= 3 ? 3 : 2)>, WideGeom<4, T>::LDS);
-#define SETW2(T) \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<2, T, MB_SLAB>, WideGeom<2, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<2, T, MB_QKV>, WideGeom<2, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_SLAB>, WideGeom<4, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_QKV>, WideGeom<4, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<2, T, MB_SLAB, 0, (T >= 3 ? 3 : 2)>, WideGeom<2, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<2, T, MB_QKV, 0, (T >= 3 ? 3 : 2)>, WideGeom<2, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_SLAB, 0, (T >= 3 ? 3 : 2)>, WideGeom<4, T>::LDS); \
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, T, MB_QKV, 0, (T >= 3 ? 3 : 2)>, WideGeom<4, T>::LDS);
-    SETW4(2) SETW4(3) SETW4(4) SETW2(1) SETW2(2)
-#undef SETW4
-#undef SETW2
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 2, MB_SLAB, 4>, WideGeom<4, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 2, MB_QKV, 4>, WideGeom<4, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<8, 2, MB_QKV>, WideGeom<8, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<8, 2, MB_QKV, 0, 2>, WideGeom<8, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 4, MB_SWIGLU, 1>, WideGeom<4, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 4, MB_SWIGLU, 2>, WideGeom<4, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 4, MB_SWIGLU, 3>, WideGeom<4, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 4, MB_SWIGLU, 4>, WideGeom<4, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 4, MB_SWIGLU, 5>, WideGeom<4, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_wide<4, 4, MB_SWIGLU, 6, 3>, WideGeom<4, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<8, 2, MB_SWIGLU>, FatGeom<8, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<8, 3, MB_SWIGLU>, FatGeom<8, 3>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<8, 4, MB_SWIGLU>, FatGeom<8, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 2, MB_SLAB, 4, 0, 4, 2>, FatGeom<4, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fatd<4, 0>, LA_FATD_LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fatd<3, 0>, LA_FATD_LDS);
-#if LA_LAB
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<8, 2, MB_SWIGLU, 4, 0, 4, 1>, FatGeom<8, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<8, 3, MB_SWIGLU, 4, 0, 4, 1>, FatGeom<8, 3>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<8, 4, MB_SWIGLU, 4, 0, 4, 1>, FatGeom<8, 4>::LDS);
-#endif
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 2, MB_SWIGLU, 4, 2>, FatGeom<4, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 3, MB_SWIGLU, 4, 2>, FatGeom<4, 3>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 4, MB_SWIGLU, 4, 2>, FatGeom<4, 4>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 1, MB_SLAB>, FatGeom<4, 1>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 2, MB_SLAB>, FatGeom<4, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<2, 2, MB_SLAB, 4, 2, 2>, FatGeom<2, 2, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<2, 2, MB_QKV, 4, 2, 2>, FatGeom<2, 2, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<2, 2, MB_QKV, 2, 2, 2>, FatGeom<2, 2, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<2, 2, MB_QKV, 4, 0, 2>, FatGeom<2, 2, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<2, 2, MB_QKV, 2, 0, 2>, FatGeom<2, 2, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<2, 1, MB_QKV, 4, 0, 2>, FatGeom<2, 1, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<2, 1, MB_QKV, 2, 0, 2>, FatGeom<2, 1, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 1, MB_QKV, 4>, FatGeom<4, 1>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 2, MB_QKV, 4>, FatGeom<4, 2>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 1, MB_QKV, 2>, FatGeom<4, 1>::LDS);
-    if (e == hipSuccess) e = set_lds(k_gemm_fat<4, 2, MB_QKV, 2>, FatGeom<4, 2>::LDS);
+    for (int i = 0; i < MBF_COUNT && e == hipSuccess; ++i)
+        e = hipFuncSetAttribute(kMbKernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, kMbForms[i].lds);
     if (e == hipSuccess) e = set_lds(k_tree_attn_mb<false, true>, 8 * 66 * 64 * 4 + 16384);
     if (e == hipSuccess) e = set_lds(k_tree_attn_mb<false, false>, 8 * 66 * 64 * 4 + 16384);
     if (e == hipSuccess) e = set_lds(k_tree_attn_mb<true, true>, 8 * 66 * 64 * 4 + 16384);
@@ -2786,270 +2725,30 @@ int lk_mb_moe_accum_norm(hipStream_t st, const float* slabs0, long slab_stride, 
 
 int lk_mb_cand_slots(int n_wg) { return n_wg * 4; }
 
-template <int RBV, int EPI>
-static int launch_mb(hipStream_t st, const MbArgs& a, int n_wg, int ksplit, int nblk) {
-    // mb_k_range cuts an even K16 on even k-tiles: with fewer than two k-tiles per split a split would be EMPTY (t0 == t1), which only the
-    // fat launches guard against — k_gemm_wide's DMA clamp (t1 - 1) would read below its range.  No engine shape gets here (resolve_cfg keeps
-    // >= 4 k-tiles per split); refuse instead of computing garbage.
-    if (ksplit < 1 || (ksplit > 1 && a.K16 < 2 * ksplit)) return -1;
-    if (a.nblk_dev) {
-        // gathered expert: the block count is a device value (typically 1-2 of the step's nblk): passes of two blocks, a pass
-        // past the expert's count returns before it touches the weights
-        if constexpr (EPI == MB_SLAB || EPI == MB_SWIGLU) {
-            if (a.ex_n > 1 && (g_la_ex_d4 & (RBV == 4 ? 4 : 8)) && n_wg % 2 == 0 && (EPI == MB_SLAB || (a.planned && !a.gu_interleaved))) {
-                // round 5 (la_lab_set key 25, bit 2 = gate/up, bit 3 = down): TWO adjacent weight regions per workgroup.  Every workgroup of an
-                // expert stages the expert's whole x through LDS: 0.5-1.8 MB from L2 per 0.9 MB of weights from HBM, and the per-CU times of
-                // the two ADD (T = W / 25 GB/s + x / 130 GB/s) — the gap between these launches (4.6-5.2 TB/s of weights) and the
-                // dense 64-row kernels (5.9).  With two regions per workgroup the x traffic and the LDS reads per weight byte halve: the 8 waves
-                // are 2 RBV row-blocks x 4 / RBV K parts (gate/up: one row-block per wave over the whole K range; down: 2 K parts instead of 4).
-                // FEWER K parts = ANOTHER fp32 summation order than the one-region launch: results agree to tolerance, not bitwise
-                // (include/lookahead_hip_lab.h key 25; tests/test_gpu_mblock.py::test_merged_expert_launch_forms_agree asserts 1e-2) —
-                // so Mixtral's default numerics moved by that much when this form became the default in round 5.
-                MbArgs p = a;
-                if (p.planned) {
-                    for (int i = 0; i < 4; ++i) { p.boff[4 + i] = a.wg_chunks + a.boff[i]; p.nv[4 + i] = a.nv[i]; p.nvl[4 + i] = a.nvl[i]; }
-                    p.wg_chunks = 2 * a.wg_chunks;
-                }
-                k_gemm_mb<2 * RBV, 4, EPI, true><<<dim3(n_wg / 2, ksplit, (nblk + 1) / 2 * a.ex_n), 512, mb_lds(4), st>>>(p);
-                LAUNCH_CHECK(); return 0;
-            }
-            if (a.ex_n > 1) {
-                // two workgroups per CU (D = 4, <= 128 VGPRs): la_lab_set key 25 bit 0 = the gate/up launch (default on: Mixtral bs=4
-                // 21.0-21.5 -> 20.1-20.2 ms per step), bit 1 = the down launch (RBV = 2: 44 B per lane of scratch at that bound)
-                if (g_la_ex_d4 & (RBV == 4 ? 1 : 2)) k_gemm_mb<RBV, 4, EPI, true, 4><<<dim3(n_wg, ksplit, (nblk + 1) / 2 * a.ex_n), 512, mb_lds(4), st>>>(a);
-                else k_gemm_mb<RBV, 4, EPI, true><<<dim3(n_wg, ksplit, (nblk + 1) / 2 * a.ex_n), 512, mb_lds(4), st>>>(a);
-                LAUNCH_CHECK(); return 0;
-            }
-        }
-        k_gemm_mb<RBV, 4, EPI><<<dim3(n_wg, ksplit, (nblk + 1) / 2), 512, mb_lds(4), st>>>(a);
-        LAUNCH_CHECK(); return 0;
-    }
-    // nblk >= 3: every token block in ONE weight pass (k_gemm_wide): RBV = 4 -> 4 TW token blocks per workgroup, RBV = 2 -> 8 TW
-    if (nblk >= 3 && !g_la_mb_narrow) {
-        const dim3 grid(n_wg, ksplit, 1);
-#if LA_LAB
-        if constexpr (RBV == 4 && EPI == MB_SWIGLU) {           // measurement builds of the 512-row gate/up launch (la_debug_set key 4)
-            if (g_la_mb_dbg == 6 && nblk >= 7) {
-                MbArgs p = a; p.dbg_times = g_la_dbg_times;
-                k_gemm_wide<4, 4, MB_SWIGLU, 6, 3><<<grid, 512, WideGeom<4, 4>::LDS, st>>>(p);
-                LAUNCH_CHECK(); return 0;
-            }
-            if (g_la_mb_dbg && nblk >= 7) {
-                if (g_la_mb_dbg == 1) k_gemm_wide<4, 4, MB_SWIGLU, 1><<<grid, 512, WideGeom<4, 4>::LDS, st>>>(a);
-                else if (g_la_mb_dbg == 2) k_gemm_wide<4, 4, MB_SWIGLU, 2><<<grid, 512, WideGeom<4, 4>::LDS, st>>>(a);
-                else if (g_la_mb_dbg == 3) k_gemm_wide<4, 4, MB_SWIGLU, 3><<<grid, 512, WideGeom<4, 4>::LDS, st>>>(a);
-                else if (g_la_mb_dbg == 4) k_gemm_wide<4, 4, MB_SWIGLU, 4><<<grid, 512, WideGeom<4, 4>::LDS, st>>>(a);
-                else k_gemm_wide<4, 4, MB_SWIGLU, 5><<<grid, 512, WideGeom<4, 4>::LDS, st>>>(a);
-                LAUNCH_CHECK(); return 0;
-            }
-        }
-#endif
-        if constexpr (RBV == 2) {
-            // Paired form (MB_SLAB, MB_QKV): TWO adjacent weight regions per workgroup and HALF the token blocks — the RBV = 4 wave
-            // grid (2 row groups x 4 token groups) over regions {2 x, 2 x + 1}, grid.z = 2 token halves.  Every workgroup re-reads the
-            // whole x operand of its token blocks from L2 (1 GB per launch at 512 rows and 256 workgroups: the dominant term of these
-            // launches); pairing halves that, and the second reader of a weight region (z = 1, 128 workgroup ids later: same XCD)
-            // finds it in L2.  Same MFMAs on the same operands in the same order per output: bit-identical results.
-            // Quad form (MB_QKV of a GQA model at >= 7 blocks: small N, many rows — the x re-reads dominate): FOUR adjacent regions and
-            // a QUARTER of the token blocks per workgroup.  L2 -> LDS traffic of the launch = x bytes x (workgroup columns) + W bytes x
-            // (token groups): Mistral QKV at 512 rows 512 + 100 MB paired -> 256 + 200 MB quad; not taken where W dominates
-            // (MHA / 13B shapes, <= 4 blocks).  Same MFMA chain per output element: bit-identical to the paired and unpaired forms.
-            if constexpr (EPI == MB_QKV) {
-                const double xb = (double)nblk * 64 * a.K16 * 32, wb = (double)a.N * a.K16 * 32;       // bytes of x and of W
-                const double paired = xb * (n_wg / 2) + wb * ((nblk + 3) / 4), quad = xb * (n_wg / 4) + wb * ((nblk + 1) / 2);
-                if ((g_la_mb_pair & 4) && a.planned && nblk >= 7 && n_wg % 4 == 0 && (n_wg / 4 * ksplit) % 8 == 0 && quad < 0.85 * paired) {
-                    MbArgs p = a;
-                    p.w_keep = 1;
-                    for (int r = 1; r < 4; ++r)
-                        for (int j = 0; j < 2; ++j) {
-                            p.boff[2 * r + j] = r * a.wg_chunks + a.boff[j]; p.nv[2 * r + j] = a.nv[j]; p.nvl[2 * r + j] = a.nvl[j];
-                        }
-                    p.wg_chunks = 4 * a.wg_chunks;
-                    wide_launch<8, 2, EPI>(dim3(n_wg / 4, ksplit, (nblk + 1) / 2), st, p);
-                    LAUNCH_CHECK(); return 0;
-                }
-            }
-            if constexpr (EPI == MB_QKV) {
-                // round 5 (bit 8 of key 6): ONE {lo, hi} region x 256 rows per workgroup as four fat waves of 2 row-blocks x 2 token blocks.
-                // The paired quarters give a CU TWO regions' weights for 128 rows, and the token groups run in lockstep, so every CU waits for
-                // its weights at the HBM-class rate: 1.05 MB per CU at the Mistral shape (512 rows) = the 42 of the launch's 45 us.  One
-                // region x 256 rows: half the weight bytes per CU, twice the x (which comes from L2).  Taken at <= 4 blocks, and at 5-8
-                // blocks when the two token halves still fit one wave of workgroups (the fuller QKV image of a GQA model: 96 x 2).
-                // bit 12 of key 6: the same one-region form with ONE token tile per wave (128 rows per workgroup, grid.z = pairs of blocks) where 256
-                // rows per workgroup leave most of the chip idle — the fuller GQA image (Mistral / Mixtral: 96 regions) at 3-4 blocks is 96
-                // workgroups on 256 CUs, each waiting for 0.5 MB of weights at the HBM-class per-CU rate; two token groups = 192 workgroups
-                // (the second reader of a region finds it in L2).  <= 2 blocks: the 2 x 2 form would run MFMAs on absent blocks.
-                if ((g_la_mb_pair & 4096) != 0 && (g_la_mb_pair & 256) != 0 && ksplit == 1 && (a.K16 & 1) == 0 && (a.R & 1) == 0 && g_la_mb_dbg == 0 && nblk <= 4 && (nblk <= 2 || n_wg <= 128)) {
-                    const dim3 gq(n_wg, 1, (nblk + 1) / 2);
-                    if ((a.R & 3) == 0) k_gemm_fat<2, 1, MB_QKV, 4, 0, 2><<<gq, 256, FatGeom<2, 1, 2>::LDS, st>>>(a);
-                    else k_gemm_fat<2, 1, MB_QKV, 2, 0, 2><<<gq, 256, FatGeom<2, 1, 2>::LDS, st>>>(a);
-                    LAUNCH_CHECK(); return 0;
-                }
-                const int zq = (nblk + 3) / 4;
-                // Measured (profiles/r05_fat_waves.txt, call 7): 13B bs=4 10.64 -> 10.59 ms, Mixtral bs=4 19.65 -> 19.41 at 4 blocks; Mistral bs=8
-                // (8 blocks, two token halves) 9.465 -> 9.489: taken at <= 4 blocks only (bit 9 forces the 5-8 block form: measurement).
-                if ((g_la_mb_pair & 256) && ksplit == 1 && (a.K16 & 1) == 0 && (a.R & 1) == 0 && g_la_mb_dbg == 0 && (zq == 1 || ((g_la_mb_pair & 512) && n_wg * zq <= 256))) {
-                    const dim3 gq(n_wg, 1, zq);
-                    if (zq == 1) {
-                        if ((a.R & 3) == 0) k_gemm_fat<2, 2, MB_QKV, 4, 2, 2><<<gq, 256, FatGeom<2, 2, 2>::LDS, st>>>(a);
-                        else k_gemm_fat<2, 2, MB_QKV, 2, 2, 2><<<gq, 256, FatGeom<2, 2, 2>::LDS, st>>>(a);
-                    } else {
-                        if ((a.R & 3) == 0) k_gemm_fat<2, 2, MB_QKV, 4, 0, 2><<<gq, 256, FatGeom<2, 2, 2>::LDS, st>>>(a);
-                        else k_gemm_fat<2, 2, MB_QKV, 2, 0, 2><<<gq, 256, FatGeom<2, 2, 2>::LDS, st>>>(a);
-                    }
-                    LAUNCH_CHECK(); return 0;
-                }
-            }
-            if constexpr (EPI == MB_SLAB) {
-                // round 5 (bit 10 of key 6): the slab launches (o_proj / down) at <= 4 blocks as ONE 64-row weight region x 256 rows per workgroup
-                // (four fat waves of 2 row-blocks x 2 token blocks) instead of two regions x 128 rows: half the weight bytes per CU at the
-                // HBM-class rate, twice the x from L2 — the trade that paid for gate/up and QKV at 256 rows.  Measured SLOWER here (13B bs=4 10.50 ->
-                // 10.63 ms, Mixtral bs=4 19.15 -> 19.45, profiles/r05_fat_waves.txt call 8): opt-in, bit-identical.
-                if ((g_la_mb_pair & 1024) && nblk <= 4 && (a.K16 & 1) == 0 && a.K16 >= 2 * ksplit && g_la_mb_dbg == 0 && !a.planned) {
-                    k_gemm_fat<2, 2, MB_SLAB, 4, 2, 2><<<dim3(n_wg, ksplit, 1), 256, FatGeom<2, 2, 2>::LDS, st>>>(a);
-                    LAUNCH_CHECK(); return 0;
-                }
-            }
-            if ((g_la_mb_pair & 1) && n_wg % 2 == 0 && (n_wg / 2 * ksplit) % 8 == 0) {
-                MbArgs p = a;
-                p.w_keep = 1;
-                if (p.planned) {
-                    p.boff[2] = a.wg_chunks + a.boff[0]; p.boff[3] = a.wg_chunks + a.boff[1];
-                    p.nv[2] = a.nv[0]; p.nv[3] = a.nv[1]; p.nvl[2] = a.nvl[0]; p.nvl[3] = a.nvl[1];
-                    p.wg_chunks = 2 * a.wg_chunks;
-                }
-                // la_debug_set key 12 (slab launches with <= 2 K splits): more token groups instead — 2 blocks per workgroup at every block count
-                // QKV over at most 128 (fuller) workgroups — the multi-block image of a GQA model, cfg.qkv_mb_wg — takes token QUARTERS at
-                // every block count: n_wg / 2 x 4 <= 256 workgroups of 4 row-blocks x 4 token tiles (la_debug_set(6, 9) forces the form)
-                // round 5 (bit 5 of key 6): the paired slab / QKV launches as four fat waves of 4 row-blocks x TW token blocks (k_gemm_fat);
-                // every K split must hold an even number of k-tiles
-                const bool fat = (g_la_mb_pair & 32) && (a.K16 & 1) == 0 && a.K16 >= 2 * ksplit && g_la_mb_dbg == 0;
-                const bool quarters = nblk <= 4 || (EPI == MB_SLAB && g_la_mb_ks2 && ksplit <= 2) || (EPI == MB_QKV && (n_wg <= 128 || (g_la_mb_pair & 8)));
-                if constexpr (EPI == MB_SLAB) {
-                    if (fat) {
-                        const dim3 gs(n_wg / 2, ksplit, quarters ? (nblk + 1) / 2 : (nblk + 3) / 4);
-                        // bit 13 of key 6: one K split per XCD (k_gemm_fat, MbArgs.xcd_map) — 2 / 4 / 8 splits over a grid of a multiple of 8 workgroups
-                        // (bit 14: also on grids that are not whole multiples of 256 workgroups — the forced-4-split 13B launch over 160 workgroups that measured
-                        //  30 % slower with the mapping, profiles/r05_fat_waves.txt call 14: measurement only)
-                        const unsigned total = gs.x * gs.y * gs.z;
-                        p.xcd_map = ((g_la_mb_pair & 8192) && (ksplit == 2 || ksplit == 4 || ksplit == 8) && total % 8 == 0 && (total % 256 == 0 || (g_la_mb_pair & 16384))) ? 1 : 0;
-                        // round 6 (late; knob 36, default on): the two-token-tile form with x DIRECT (k_gemm_fat, STG = 2): 43.1 -> 41.2 us per launch at the
-                        // Mistral shape, 512 rows.  The other one-row-group forms (quarters, QKV, one-region gate/up) measured level or slower with it.
-                        if (g_la_fatx && !quarters) k_gemm_fat<4, 2, EPI, 4, 0, 4, 2><<<gs, 256, FatGeom<4, 2>::LDS, st>>>(p);
-                        else if (quarters) k_gemm_fat<4, 1, EPI><<<gs, 256, FatGeom<4, 1>::LDS, st>>>(p);
-                        else k_gemm_fat<4, 2, EPI><<<gs, 256, FatGeom<4, 2>::LDS, st>>>(p);
-                        LAUNCH_CHECK(); return 0;
-                    }
-                }
-                if constexpr (EPI == MB_QKV) {
-                    if (fat && (a.R & 1) == 0) {              // RoPE pairs per workgroup: groups of 4 (7B, Mistral, Mixtral) or 2 (13B) rows per store
-                        const dim3 gq(n_wg / 2, ksplit, quarters ? (nblk + 1) / 2 : (nblk + 3) / 4);
-                        if ((a.R & 3) == 0) {
-                            if (quarters) k_gemm_fat<4, 1, EPI, 4><<<gq, 256, FatGeom<4, 1>::LDS, st>>>(p);
-                            else k_gemm_fat<4, 2, EPI, 4><<<gq, 256, FatGeom<4, 2>::LDS, st>>>(p);
-                        } else {
-                            if (quarters) k_gemm_fat<4, 1, EPI, 2><<<gq, 256, FatGeom<4, 1>::LDS, st>>>(p);
-                            else k_gemm_fat<4, 2, EPI, 2><<<gq, 256, FatGeom<4, 2>::LDS, st>>>(p);
-                        }
-                        LAUNCH_CHECK(); return 0;
-                    }
-                }
-                if (quarters) wide_launch<4, 1, EPI>(dim3(n_wg / 2, ksplit, (nblk + 1) / 2), st, p);
-#if LA_LAB
-                else if (g_la_mb_dbg == 4) k_gemm_wide<4, 2, EPI, 4><<<dim3(n_wg / 2, ksplit, (nblk + 3) / 4), 512, WideGeom<4, 2>::LDS, st>>>(p);   // measurement: no epilogue
-#endif
-                else wide_launch<4, 2, EPI>(dim3(n_wg / 2, ksplit, (nblk + 3) / 4), st, p);
-                LAUNCH_CHECK(); return 0;
-            }
-        }
-        if constexpr (RBV == 4 && EPI == MB_SWIGLU) {
-            // round 5 (bit 6 of key 6): ONE planned region x ALL token blocks per workgroup as four fat waves (4 row-blocks x TW token blocks each,
-            // 1 x 4 wave grid).  The paired fat form makes every CU pull TWO regions' weights, and since the two token halves run in lockstep
-            // both wait for the same HBM miss: 1.83 MB per CU at the HBM-class per-CU rate (~25 GB/s) = 73 us of the 103-113 us launch at the
-            // Mistral shape, 512 rows.  One region per workgroup: 0.92 MB of weights (nt) + 4 MB of x from L2 (~130 GB/s) per CU.
-            // Measured (profiles/r05_fat_waves.txt, call 6): it wins at <= 4 blocks (13B 256 rows 90.3 -> 84.6 us, 13B bs=4 10.77 -> 10.63 ms per
-            // step) and LOSES at 512 rows (Mistral 115.8 -> 121.2 us: 4 MB of x per CU instead of 2) — so it is taken at <= 4 blocks only;
-            // bit 7 forces it at every block count (measurement).
-            if ((g_la_mb_pair & 64) && a.planned && !a.gu_interleaved && ksplit == 1 && (a.K16 & 1) == 0 && (nblk <= 4 || ((g_la_mb_pair & 128) && nblk <= 8))) {
-                const dim3 g1(n_wg, 1, 1);
-                switch ((nblk + 1) / 2) {
-                    case 2: k_gemm_fat<4, 2, MB_SWIGLU, 4, 2><<<g1, 256, FatGeom<4, 2>::LDS, st>>>(a); break;
-                    case 3: k_gemm_fat<4, 3, MB_SWIGLU, 4, 2><<<g1, 256, FatGeom<4, 3>::LDS, st>>>(a); break;
-                    default: k_gemm_fat<4, 4, MB_SWIGLU, 4, 2><<<g1, 256, FatGeom<4, 4>::LDS, st>>>(a); break;
-                }
-                LAUNCH_CHECK(); return 0;
-            }
-            // paired gate/up launch (planned images): regions {2 x, 2 x + 1} = row-blocks 0..7, half the token blocks per workgroup.
-            // Bit-identical, but NOT faster (this launch is bound by its MFMA / ds_read side, not by the x traffic: 512 rows 116.5 vs
-            // 116.4 us, 256 rows 68.4 vs 76.6 us at the 7B shape, profiles/r02b_mblock_paired_ab.txt): opt-in (la_debug_set(6, 3)).
-            if ((g_la_mb_pair & (2 | 16)) && a.planned && !a.gu_interleaved && n_wg % 16 == 0 && ksplit == 1) {
-                const bool fat = (g_la_mb_pair & 16) && (a.K16 % 2) == 0;
-                MbArgs p = a;
-                p.w_keep = 1;
-                for (int i = 0; i < 4; ++i) { p.boff[4 + i] = a.wg_chunks + a.boff[i]; p.nv[4 + i] = a.nv[i]; p.nvl[4 + i] = a.nvl[i]; }
-                p.wg_chunks = 2 * a.wg_chunks;
-                const dim3 g2(n_wg / 2, 1, 2);
-                if (fat) {
-                    // round 5: the same pair of regions as FOUR fat waves (4 x TW accumulator tiles each, one wave per SIMD): k_gemm_fat
-#if LA_LAB
-                    if (g_la_mb_pair & 2048) {                  // bit 11: the register-staged form (k_gemm_fat, STG = 1)
-                        switch ((nblk + 1) / 2) {
-                            case 2: k_gemm_fat<8, 2, MB_SWIGLU, 4, 0, 4, 1><<<g2, 256, FatGeom<8, 2>::LDS, st>>>(p); break;
-                            case 3: k_gemm_fat<8, 3, MB_SWIGLU, 4, 0, 4, 1><<<g2, 256, FatGeom<8, 3>::LDS, st>>>(p); break;
-                            default: k_gemm_fat<8, 4, MB_SWIGLU, 4, 0, 4, 1><<<g2, 256, FatGeom<8, 4>::LDS, st>>>(p); break;
-                        }
-                        LAUNCH_CHECK(); return 0;
-                    }
-#endif
-                    // lab knob 35 (round 6, late): weights straight into MFMA operand registers (k_gemm_fatd), 7-8 blocks, K16 % 8 == 0
-                    // round 6 (late; knob 35, default on): weights straight into MFMA operand registers (k_gemm_fatd) at 5-8 blocks (an even number of
-                    // k-tiles).  Measured (profiles/r06_gateup_direct_weights.txt): 512 rows 115.4 -> 109.1 us per launch at the Mistral
-                    // shape, Mistral bs=8 9.55 -> 9.36 ms per step, Llama-2-7B bs=8 9.94 -> 9.76; bit-identical.
-                    if (g_la_fatd && (nblk + 1) / 2 >= 3 && (a.K16 & 1) == 0 && a.R <= 64) {
-                        if ((nblk + 1) / 2 == 4) k_gemm_fatd<4, 0><<<g2, 256, LA_FATD_LDS, st>>>(p);
-                        else k_gemm_fatd<3, 0><<<g2, 256, LA_FATD_LDS, st>>>(p);
-                        LAUNCH_CHECK(); return 0;
-                    }
-                    switch ((nblk + 1) / 2) {
-                        case 2: k_gemm_fat<8, 2, MB_SWIGLU><<<g2, 256, FatGeom<8, 2>::LDS, st>>>(p); break;
-                        case 3: k_gemm_fat<8, 3, MB_SWIGLU><<<g2, 256, FatGeom<8, 3>::LDS, st>>>(p); break;
-                        default: k_gemm_fat<8, 4, MB_SWIGLU><<<g2, 256, FatGeom<8, 4>::LDS, st>>>(p); break;
-                    }
-                    LAUNCH_CHECK(); return 0;
-                }
-                switch ((nblk + 1) / 2) {                       // 64-row blocks per workgroup = TW
-                    case 2: wide_launch<8, 2, EPI>(g2, st, p); break;
-                    case 3: wide_launch<8, 3, EPI>(g2, st, p); break;
-                    default: wide_launch<8, 4, EPI>(g2, st, p); break;
-                }
-                LAUNCH_CHECK(); return 0;
-            }
-        }
-        if constexpr (RBV == 4) {
-            switch ((nblk + 1) / 2) {
-                case 2: wide_launch<4, 2, EPI>(grid, st, a); break;
-                case 3: wide_launch<4, 3, EPI>(grid, st, a); break;
-                default: wide_launch<4, 4, EPI>(grid, st, a); break;
-            }
-        } else {
-            if (nblk <= 4) wide_launch<2, 1, EPI>(dim3(n_wg, ksplit, (nblk + 3) / 4), st, a);
-            else wide_launch<2, 2, EPI>(grid, st, a);
-        }
-        LAUNCH_CHECK(); return 0;
-    }
-    // token blocks per pass: the smallest template that covers the step in <= 2 passes
-    if (nblk <= 1) { k_gemm_mb<RBV, 2, EPI><<<dim3(n_wg, ksplit, 1), 512, mb_lds(2), st>>>(a); }
-    else if (nblk == 2) { k_gemm_mb<RBV, 4, EPI><<<dim3(n_wg, ksplit, 1), 512, mb_lds(4), st>>>(a); }
-    else { k_gemm_mb<RBV, 8, EPI><<<dim3(n_wg, ksplit, (nblk + 3) / 4), 512, mb_lds(8), st>>>(a); }
-    LAUNCH_CHECK(); return 0;
+// `n` adjacent weight regions per workgroup (MbForm.regions) of `per` row-blocks each: a planned image addresses region r through plan
+// entries r * per .. — copies of the first region's, `wg_chunks` further on each; a classic image needs nothing
+static void merge_regions(MbArgs& p, int n, int per) {
+    if (!p.planned || n == 1) return;
+    for (int r = 1; r < n; ++r)
+        for (int j = 0; j < per; ++j) { p.boff[r * per + j] = r * p.wg_chunks + p.boff[j]; p.nv[r * per + j] = p.nv[j]; p.nvl[r * per + j] = p.nvl[j]; }
+    p.wg_chunks *= n;
 }
 
-static void fill_plan(MbArgs& a, int R, int bpm, int mats, int K16) {
-    for (int m = 0; m < mats; ++m)
-        for (int b = 0; b < bpm; ++b) { int v = R - 32 * b; if (v > 32) v = 32; a.nv[m * bpm + b] = v; }
-    int off = 0;
-    for (int i = 0; i < mats * bpm; ++i) { a.nvl[i] = (a.nv[i] + 3) & ~3; a.boff[i] = off; off += a.nvl[i] * 2 * K16; }
-    a.wg_chunks = off;
+// one multi-block GEMM: la_mb_select (la_mb_forms.h) picks the form, the table row gives kernel, block and LDS
+static int launch_mb(hipStream_t st, const MbArgs& a, int kind, int n_wg, int ksplit) {
+    const MbFormIn in{kind, a.nblk, n_wg, ksplit, a.K16, a.N, a.R, a.planned, a.gu_interleaved, a.ex_n, a.nblk_dev != nullptr, a.qkv_bias != nullptr};
+    const MbFormKnobs knobs{g_la_mb_pair, g_la_mb_narrow, g_la_mb_dbg, g_la_mb_sch, g_la_mb_ks2, g_la_ex_d4, g_la_fatd, g_la_fatx};
+    const MbForm f = la_mb_select(in, knobs);
+    if (f.id < 0) return -1;
+    MbArgs p = a;
+    p.w_keep = f.w_keep; p.xcd_map = f.xcd_map;
+    merge_regions(p, f.regions, (kind == MB_SLAB || kind == MB_QKV) ? 2 : 4);
+#if LA_LAB
+    if (f.id == MBF_WIDE_4_4_SWIGLU_6_3_0_0) p.dbg_times = g_la_dbg_times;          // the stamping measurement build
+#endif
+    void* args[] = {&p};
+    (void)hipLaunchKernel(kMbKernels[f.id], dim3(f.gx, f.gy, f.gz), dim3(kMbForms[f.id].block), args, kMbForms[f.id].lds, st);
+    LAUNCH_CHECK(); return 0;
 }
 
 int lk_mb_gemm(hipStream_t st, int kind, const MbGemm& g) {
@@ -3064,7 +2763,7 @@ int lk_mb_gemm(hipStream_t st, int kind, const MbGemm& g) {
     if (kind == 0) {
         if (g.N % 64) return -1;
         a.planned = 0; a.slabs = g.slabs;
-        return launch_mb<2, MB_SLAB>(st, a, g.N / 64, g.ksplit, g.nblk);
+        return launch_mb(st, a, kind, g.N / 64, g.ksplit);
     }
     a.planned = g.n_wg > 0 ? 1 : 0;
     for (int i = 0; i < 4; ++i) { a.nv[i] = 32; a.nvl[i] = 32; }
@@ -3073,37 +2772,36 @@ int lk_mb_gemm(hipStream_t st, int kind, const MbGemm& g) {
         if (!a.planned) {                          // classic interleaved gate/up image: 4 row-blocks {G,U,G,U} per workgroup
             if (g.N % 64) return -1;
             a.gu_interleaved = 1; a.R = 64;
-            return launch_mb<4, MB_SWIGLU>(st, a, g.N / 64, 1, g.nblk);
+            return launch_mb(st, a, kind, g.N / 64, 1);
         }
         a.R = g.N / g.n_wg; if (g.N % g.n_wg || a.R > 64 || a.R <= 32) return -1;
-        fill_plan(a, a.R, 2, 2, a.K16);
-        return launch_mb<4, MB_SWIGLU>(st, a, g.n_wg, 1, g.nblk);
+        a.wg_chunks = la_fill_plan(a.nv, a.nvl, a.boff, a.R, 2, 2, a.K16);
+        return launch_mb(st, a, kind, g.n_wg, 1);
     }
     if (kind == 2) {
         a.pos = g.pos; a.rcos = (const bf16_t*)g.rcos; a.rsin = (const bf16_t*)g.rsin;
         a.qf = (bf16_t*)g.qf; a.kfresh = (bf16_t*)g.kfresh; a.vfresh = (bf16_t*)g.vfresh; a.nh = g.nh; a.nkv = g.nkv;
         a.qkv_bias = (const bf16_t*)g.qkv_bias;
-        if (a.qkv_bias && g_la_mb_dbg == 4) return -1;      // the no-epilogue measurement build would drop the bias
         if (!a.planned) {                          // classic row-permuted image (la_qkv_row_perm): pair index = 32 * workgroup + f
             a.R = 32;
-            return launch_mb<2, MB_QKV>(st, a, (g.nh + 2 * g.nkv) * 2, 1, g.nblk);
+            return launch_mb(st, a, kind, (g.nh + 2 * g.nkv) * 2, 1);
         }
         const int pairs = (g.nh + 2 * g.nkv) * 64;
         a.R = pairs / g.n_wg; if (pairs % g.n_wg || a.R > 32) return -1;
         a.nv[0] = a.nv[1] = a.R; a.nvl[0] = a.nvl[1] = (a.R + 3) & ~3;
         a.boff[0] = 0; a.boff[1] = a.nvl[0] * 2 * a.K16; a.wg_chunks = 2 * a.boff[1];
-        return launch_mb<2, MB_QKV>(st, a, g.n_wg, 1, g.nblk);
+        return launch_mb(st, a, kind, g.n_wg, 1);
     }
     if (kind == 3) {
         a.logits = (bf16_t*)g.logits; a.cand_val = g.cand_val; a.cand_idx = g.cand_idx;
         if (!a.planned) {
             if (g.N % 128) return -1;
             a.R = 128;
-            return launch_mb<4, MB_LOGITS>(st, a, g.N / 128, 1, g.nblk);
+            return launch_mb(st, a, kind, g.N / 128, 1);
         }
         a.R = g.N / g.n_wg; if (g.N % g.n_wg || a.R > 128 || a.R <= 96) return -1;
-        fill_plan(a, a.R, 4, 1, a.K16);
-        return launch_mb<4, MB_LOGITS>(st, a, g.n_wg, 1, g.nblk);
+        a.wg_chunks = la_fill_plan(a.nv, a.nvl, a.boff, a.R, 4, 1, a.K16);
+        return launch_mb(st, a, kind, g.n_wg, 1);
     }
     return -1;
 }

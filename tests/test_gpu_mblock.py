@@ -983,3 +983,69 @@ def test_moe_plan_gather_one_launch_is_bitwise_the_two_launch_form():
             assert torch.equal(outs[0][0], outs[4][0]) and torch.equal(outs[0][1], outs[4][1]) and outs[0][2] == outs[4][2], B
     finally:
         _lib.lab_set(16, default_form)
+
+
+def test_every_product_gemm_form_launches_and_matches_torch():
+    """One small launch per row of the product build's table of GEMM forms (csrc/la_mb_forms.h; tests/mb_form_cases.py lists them and
+    tests/test_mb_forms_cpu.py asserts that each case selects the form it names) against the fp32 torch reference, at the tolerance this
+    file uses for the kind: a row with another kernel's LDS size, block size or kernel pointer fails to launch or computes garbage."""
+    from tests.mb_form_cases import FORM_CASES
+    from tests.test_gpu_kernels import _rope_ref
+    rc, rs_ = rope_tables(128, 1024, 10000.0, DEV)
+    for form, kind, nblk, K, shp in FORM_CASES:
+        g = torch.Generator(device=DEV).manual_seed(nblk * 1000 + K + kind)
+        x = bf(torch.randn(nblk * 64, K, generator=g, device=DEV))
+        xp = _pack_blocks(x)
+        if kind == 0:
+            N = shp
+            w = bf(torch.randn(N, K, generator=g, device=DEV) * 0.05)
+            rows = (nblk if nblk <= 2 else (nblk + 3) // 4 * 4) * 64
+            slabs = torch.full((1, rows, N), float('nan'), dtype=torch.float32, device=DEV)
+            _mb(0, gu.pack_weight(w), xp, N, K, nblk, ksplit=1, slabs=slabs, slab_rows=rows)
+            assert gu.rel_err(slabs[0, :nblk * 64], x.double() @ w.double().t()) < 2e-3, form
+        elif kind == 1:
+            F, nwg = shp
+            wg = bf(torch.randn(F, K, generator=g, device=DEV) * 0.05)
+            wu = bf(torch.randn(F, K, generator=g, device=DEV) * 0.05)
+            act = torch.zeros(8 * 64 * F, dtype=torch.bfloat16, device=DEV)
+            _mb(1, gu.pack_planned(1, [wg, wu], nwg) if nwg else gu.pack_weight(wg, wu), xp, F, K, nblk, n_wg=nwg, act=act)
+            got = gu.from_packed(act[:nblk * 64 * F].view(nblk, 64 * F), gu.xp_index(F)).float()
+            gg, uu = bf(x.float() @ wg.float().t()), bf(x.float() @ wu.float().t())
+            ref = bf(bf(torch.nn.functional.silu(gg.float())).float() * uu.float()).float().view(nblk, 64, F)
+            assert gu.rel_err(got, ref) < 2e-2, form
+            assert float((got != ref).float().mean()) < 0.02, form
+        elif kind == 2:
+            nh, nkv, nwg = shp
+            N = (nh + 2 * nkv) * 128
+            w = bf(torch.randn(N, K, generator=g, device=DEV) * 0.05)
+            pos = torch.randint(0, 900, (nblk * 64,), generator=g, device=DEV, dtype=torch.int32)
+            if nwg:
+                wp = gu.pack_planned(2, [w], nwg)
+            else:
+                perm = np.zeros(N, dtype=np.int32)
+                check(lib.la_qkv_row_perm(nh, nkv, perm.ctypes.data_as(_lib.pi32)), 'perm')
+                wp = gu.pack_weight(w[torch.from_numpy(perm.astype(np.int64)).to(DEV)].contiguous())
+            qf = torch.zeros(8 * nh * 8192, dtype=torch.bfloat16, device=DEV)
+            kf = torch.zeros(8 * nkv * 8192, dtype=torch.bfloat16, device=DEV)
+            vf = torch.zeros(8 * nkv * 8192, dtype=torch.bfloat16, device=DEV)
+            _mb(2, wp, xp, N, K, nblk, n_wg=nwg, pos=pos, rc=rc, rs_=rs_, qf=qf, kf=kf, vf=vf, nh=nh, nkv=nkv)
+            qkv = x.float() @ w.float().t()
+            q = _rope_ref(qkv[:, :nh * 128].reshape(-1, nh, 128), pos.long())
+            k = _rope_ref(qkv[:, nh * 128:(nh + nkv) * 128].reshape(-1, nkv, 128), pos.long())
+            v = qkv[:, (nh + nkv) * 128:].reshape(-1, nkv, 128)
+            for b in range(nblk):
+                rows = slice(b * 64, (b + 1) * 64)
+                got_q = gu.from_packed(qf[b * nh * 8192:(b + 1) * nh * 8192].view(nh, 8192), gu.rf_index(64)).transpose(0, 1)
+                got_k = gu.from_packed(kf[b * nkv * 8192:(b + 1) * nkv * 8192].view(nkv, 8192), gu.rf_index(64)).transpose(0, 1)
+                got_v = gu.from_packed(vf[b * nkv * 8192:(b + 1) * nkv * 8192].view(nkv, 8192), gu.vf_index(64)).transpose(0, 1)
+                for got, ref, name in ((got_q, q[rows], 'q'), (got_k, k[rows], 'k'), (got_v, v[rows], 'v')):
+                    assert gu.rel_err(got.float(), ref) < 1e-2, (form, b, name)
+        else:
+            V, nwg = shp
+            w = bf(torch.randn(V, K, generator=g, device=DEV) * 0.05)
+            n_tiles = 4 * (nwg if nwg else V // 128)
+            logits = torch.zeros(8 * 64, V, dtype=torch.bfloat16, device=DEV)
+            cv = torch.zeros(8 * n_tiles * 64, dtype=torch.float32, device=DEV)
+            ci = torch.zeros(8 * n_tiles * 64, dtype=torch.int32, device=DEV)
+            _mb(3, gu.pack_planned(0, [w], nwg) if nwg else gu.pack_weight(w), xp, V, K, nblk, n_wg=nwg, logits=logits, cv=cv, ci=ci)
+            assert gu.rel_err(logits[:nblk * 64].float(), x.double() @ w.double().t()) < 1e-2, form
