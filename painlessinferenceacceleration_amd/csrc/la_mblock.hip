@@ -1914,7 +1914,9 @@ __global__ __launch_bounds__(512) void k_moe_plan_gather_mb(const float* __restr
 // k_moe_accum_mb + k_row_norm_addend_mb in ONE launch (round 3): the row's accumulated expert outputs never leave the registers
 // on their way into the residual add and the next RMSNorm.  Same values at every rounding point: the accumulator is bf16-exact
 // after every add (index_add_ into a bf16 buffer), so "store as bf16, load as bf16" between the two kernels was the identity.
-template <int NS>
+// XC = the most experts a row may be routed to: 4 (top_k <= 4: Mixtral, the code it always ran) or LA_MOE_MAX_E (top_k 5 .. 8); the
+// launchers pick it from the model's top_k, so no row ever loses the experts past its fourth.
+template <int NS, int XC>
 __global__ __launch_bounds__(512) void k_moe_accum_norm_mb(const float* __restrict__ slabs, long ex_slab, int slab_rows,
                                                             const float* __restrict__ route_w, int n_experts, int hidden,
                                                             const int* __restrict__ pos, bf16_t* __restrict__ h,
@@ -1922,14 +1924,14 @@ __global__ __launch_bounds__(512) void k_moe_accum_norm_mb(const float* __restri
     __shared__ float sh[8];
     const int t = blockIdx.x;
     const int nchunk = hidden >> 3;
-    int sel[4], srow[4];
-    float wsel[4];
+    int sel[XC], srow[XC];
+    float wsel[XC];
     int ns = 0;
-    for (int e = 0; e < n_experts && ns < 4; ++e) {
+    for (int e = 0; e < n_experts && ns < XC; ++e) {
         const float w = route_w[(size_t)t * LA_MOE_MAX_E + e];
         if (w != 0.f) { sel[ns] = e; wsel[ns] = w; srow[ns] = pos ? pos[(size_t)t * LA_MOE_MAX_E + e] : t; ++ns; }
     }
-    for (int k = ns; k < 4; ++k) { sel[k] = 0; wsel[k] = 0.f; srow[k] = 0; }
+    for (int k = ns; k < XC; ++k) { sel[k] = 0; wsel[k] = 0.f; srow[k] = 0; }
     float vals[2][8];
     bf16x8 wv[2];
     float ss = 0.f;
@@ -1941,7 +1943,7 @@ __global__ __launch_bounds__(512) void k_moe_accum_norm_mb(const float* __restri
             wv[ci] = *(const bf16x8*)(nw + c * 8);
             float cur[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
+            for (int k = 0; k < XC; ++k)
                 if (k < ns) {
                     f32x4 v[NS][2];
 #pragma unroll
@@ -1993,23 +1995,23 @@ __global__ __launch_bounds__(512) void k_moe_accum_norm_mb(const float* __restri
     }
 }
 
-template <int NS>
+template <int NS, int XC>
 __global__ __launch_bounds__(256) void k_moe_accum_mb(const float* __restrict__ slabs, long ex_slab, int slab_rows,
                                                        const float* __restrict__ route_w, int n_experts, int hidden,
                                                        bf16_t* __restrict__ acc, const int* __restrict__ pos) {
     const int t = blockIdx.x;
-    int sel[4], srow[4];
-    float wsel[4];
+    int sel[XC], srow[XC];
+    float wsel[XC];
     int ns = 0;
-    for (int e = 0; e < n_experts && ns < 4; ++e) {
+    for (int e = 0; e < n_experts && ns < XC; ++e) {
         const float w = route_w[(size_t)t * LA_MOE_MAX_E + e];
         if (w != 0.f) { sel[ns] = e; wsel[ns] = w; srow[ns] = pos ? pos[(size_t)t * LA_MOE_MAX_E + e] : t; ++ns; }
     }
-    for (int k = ns; k < 4; ++k) { sel[k] = 0; wsel[k] = 0.f; srow[k] = 0; }
+    for (int k = ns; k < XC; ++k) { sel[k] = 0; wsel[k] = 0.f; srow[k] = 0; }
     for (int c = threadIdx.x; c < (hidden >> 3); c += 256) {
-        f32x4 v[4][NS][2];
+        f32x4 v[XC][NS][2];
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < XC; ++k)
             if (k < ns) {
 #pragma unroll
                 for (int s2 = 0; s2 < NS; ++s2) {
@@ -2020,7 +2022,7 @@ __global__ __launch_bounds__(256) void k_moe_accum_mb(const float* __restrict__ 
             }
         float cur[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < XC; ++k)
             if (k < ns) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
@@ -2699,9 +2701,10 @@ int lk_mb_moe_plan_gather(hipStream_t st, const float* route_w, int M, const voi
     LAUNCH_CHECK(); return 0;
 }
 int lk_mb_moe_accum(hipStream_t st, const float* slabs0, long slab_stride, int n_slabs, int slab_rows, const float* route_w, int E, int hidden,
-                    void* acc, int M, const int* pos) {
-    if (hidden & 7) return -1;
-#define MA(NS) k_moe_accum_mb<NS><<<M, 256, 0, st>>>(slabs0, slab_stride, slab_rows, route_w, E, hidden, (bf16_t*)acc, pos)
+                    void* acc, int M, const int* pos, int top_k) {
+    if ((hidden & 7) || top_k < 1 || top_k > LA_MOE_MAX_E) return -1;
+#define MA(NS) do { if (top_k > 4) k_moe_accum_mb<NS, LA_MOE_MAX_E><<<M, 256, 0, st>>>(slabs0, slab_stride, slab_rows, route_w, E, hidden, (bf16_t*)acc, pos); \
+                    else k_moe_accum_mb<NS, 4><<<M, 256, 0, st>>>(slabs0, slab_stride, slab_rows, route_w, E, hidden, (bf16_t*)acc, pos); } while (0)
     switch (n_slabs) {
         case 1: MA(1); break; case 2: MA(2); break; case 4: MA(4); break; case 8: MA(8); break;
         default: return -1;
@@ -2711,10 +2714,12 @@ int lk_mb_moe_accum(hipStream_t st, const float* slabs0, long slab_stride, int n
 }
 
 int lk_mb_moe_accum_norm(hipStream_t st, const float* slabs0, long slab_stride, int n_slabs, int slab_rows, const float* route_w, int E,
-                         int hidden, int M, const int* pos, void* h, const void* nw, float eps, void* xp, int cast_first) {
-    if (hidden > 8192 || (hidden & 7)) return -1;
-#define MA(NS) k_moe_accum_norm_mb<NS><<<M, 512, 0, st>>>(slabs0, slab_stride, slab_rows, route_w, E, hidden, pos, (bf16_t*)h, \
-                                                           (const bf16_t*)nw, eps, (bf16_t*)xp, cast_first)
+                         int hidden, int M, const int* pos, void* h, const void* nw, float eps, void* xp, int cast_first, int top_k) {
+    if (hidden > 8192 || (hidden & 7) || top_k < 1 || top_k > LA_MOE_MAX_E) return -1;
+#define MA(NS) do { if (top_k > 4) k_moe_accum_norm_mb<NS, LA_MOE_MAX_E><<<M, 512, 0, st>>>(slabs0, slab_stride, slab_rows, route_w, E, hidden, pos, (bf16_t*)h, \
+                                                                                             (const bf16_t*)nw, eps, (bf16_t*)xp, cast_first); \
+                    else k_moe_accum_norm_mb<NS, 4><<<M, 512, 0, st>>>(slabs0, slab_stride, slab_rows, route_w, E, hidden, pos, (bf16_t*)h, \
+                                                                       (const bf16_t*)nw, eps, (bf16_t*)xp, cast_first); } while (0)
     switch (n_slabs) {
         case 1: MA(1); break; case 2: MA(2); break; case 4: MA(4); break; case 8: MA(8); break;
         default: return -1;

@@ -68,6 +68,8 @@ def test_mixtral_engine_matches_reference_and_oracle():
     bf16-level differences of the router input), so parity is stated in three parts:
       (1) routing: on every decisively routed row (p_k - p_(k+1) > GAP in the oracle) the engine picks the oracle's
           experts in every layer, with weights within 5e-2 (softmax slope x bf16 noise of the router logits);
+          the EXACT statement of this part — expert choice and weights on every row, ties included, for equality — is the routing
+          census (tests/moe_census.py, tests/test_gpu_moe_census.py);
       (2) continuous part: ALL rows match the oracle re-run with the engine's own routing forced (TOL_MOE);
       (3) reference: rows whose attention span holds no row with a swapped expert match the REFERENCE
           MixtralForCausalLM logits and the oracle's own-routing logits (5e-2: routing WEIGHTS still differ at the 1e-2
