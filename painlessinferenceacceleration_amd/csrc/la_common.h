@@ -192,6 +192,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// The candidate rule of every argmax of the library (GEMM logits epilogues, candidate merges, the penalised and the sampled row stages):
+// the larger value wins, among equal values the lower index (torch.argmax on CPU returns the first maximum); a NaN never wins.
+__device__ __forceinline__ void argmax_better(float v, int idx, float& best, int& bidx) {
+    if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
+}
+// ... against the candidate of the lane `o` lanes across (a butterfly step); o = 32 merges the two halves of a wave, which hold the
+// two row groups (hh = lane >> 5) of one token column of an MFMA tile
+__device__ __forceinline__ void argmax_merge_xor(float& best, int& bidx, int o) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bidx, o, 64);
+    argmax_better(ob, oi, best, bidx);
+}
+__device__ __forceinline__ void argmax_merge_halves(float& best, int& bidx) { argmax_merge_xor(best, bidx, 32); }
+
 // Router tail of a Mixtral row (MixtralSparseMoeBlock.forward, mixtral/modeling_mixtral.py:723-729): softmax over the experts' logits in
 // fp32, top-k, renormalise, cast back.  Called by ALL 64 lanes of wave 0 after the per-wave partial logits shr[wave][e] are in LDS; lane e
 // (< E) owns expert e and writes route_row[e] (weight of expert e for this row, 0 = not routed).  Bit-identical to the one-thread form it

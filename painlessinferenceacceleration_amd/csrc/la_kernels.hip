@@ -5,6 +5,7 @@
 #include <type_traits>
 #include "la_kernels.h"
 #include "la_knobs.h"
+#include "la_epilogue.h"
 
 // ---------------------------------------------------------------------------------------------
 // Layout converters (one-off at load time / tests)
@@ -657,12 +658,7 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
         for (int gg = 0; gg < GPW; ++gg) {
             bf16x4 pk;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float gv = bfr(fin[0][gg][j]);
-                float uv = bfr(fin[RB - 1][gg][j]);
-                float sv = bfr(gv / (1.0f + expf(-gv)));
-                pk[j] = (short)f2bf(sv * uv);
-            }
+            for (int j = 0; j < 4; ++j) pk[j] = (short)swiglu_act<false>(fin[0][gg][j], fin[RB - 1][gg][j]);
             const int f = jb * 32 + 8 * (g0 + gg) + 4 * hh;    // 4 consecutive features f..f+3
             *(bf16x4*)(a.act_xp + (EX ? (size_t)ex * a.ex_act : (size_t)0) + xp_offset(tok, f)) = pk;
         }
@@ -671,6 +667,8 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
         // partners 64+32u+[0,32) (rows permuted at pack time).  q/k: rotate-half RoPE in bf16 arithmetic
         // (apply_rotary_pos_emb, modeling_llama.py:154-169) -> QF / fresh KF fragments; v -> fresh VF fragments.
         static_assert(EPI != EPI_QKV || RB == 2, "qkv epilogue needs the (d, d+64) row-block pair");
+        // Kept inline, not qkv_store<4> (la_epilogue.h, the same arithmetic): through it the fp16 build's outputs of this kernel moved off
+        // the recorded ones — which RoPE product the compiler keeps rounded beside its v_fma_f16 follows the code shape (see rope_half).
         const int slot = bp.bx >> 1, u = bp.bx & 1;
 #pragma unroll
         for (int gg = 0; gg < GPW; ++gg) {
@@ -712,16 +710,12 @@ __device__ __forceinline__ void gemm64_body(const bf16_t* __restrict__ wp_s, con
                 for (int j = 0; j < 4; ++j) {
                     bf16_t hv = f2bf(fin[rb][gg][j]);
                     pk[j] = (short)hv;
-                    float v = bf2f(hv);
-                    int idx = (nb0 + rb) * 32 + 8 * (g0 + gg) + 4 * hh + j;
-                    if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
+                    argmax_better(bf2f(hv), (nb0 + rb) * 32 + 8 * (g0 + gg) + 4 * hh + j, best, bidx);
                 }
                 if (a.logits)
                     *(bf16x4*)(a.logits + (size_t)tok * a.N + (nb0 + rb) * 32 + 8 * (g0 + gg) + 4 * hh) = pk;
             }
-        float ob = __shfl_xor(best, 32, 64);
-        int oi = __shfl_xor(bidx, 32, 64);
-        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+        argmax_merge_halves(best, bidx);
         if (hh == 0) {      // candidate slot: (workgroup, register-group owner) x token
             const size_t slot = (size_t)bp.bx * (NW / 2) + (wave >> 1);
             a.cand_val[slot * LA_TB + tok] = best;
@@ -942,13 +936,9 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
             const int f0 = 8 * gi + 4 * hh;
             const bool live = f0 < ra.nv[0];
             const int pr = ra.R * bp.bx + f0, slot = pr >> 6, dlo = pr & 63, dhi = dlo + 64;
-            const bool rope = slot < a.nh + a.nkv;
-            bf16x4 c4 = {0, 0, 0, 0}, s4 = {0, 0, 0, 0};
-            if (live && rope) {          // dependent pos -> cos/sin loads are in flight across the barrier
-                const int ps = a.pos[tok];
-                c4 = *(const bf16x4*)(a.rcos + (size_t)ps * 64 + dlo);
-                s4 = *(const bf16x4*)(a.rsin + (size_t)ps * 64 + dlo);
-            }
+            const QkvDst qd = qkv_dst(a, false);
+            RopeTab<4> rt = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+            if (live && slot < a.nh + a.nkv) rt = rope_tab_load<4>(qd, a.pos[tok], dlo);          // dependent pos -> cos/sin loads, in flight across the barrier
             __syncthreads();
             if (!live) return;
             f32x4 xl = {0.f, 0.f, 0.f, 0.f}, xh = {0.f, 0.f, 0.f, 0.f};
@@ -961,28 +951,7 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                 xl *= *(const f32x4*)(wsc + slot * 128 + dlo);
                 xh *= *(const f32x4*)(wsc + slot * 128 + dhi);
             }
-            qkv_bias_add<4>(a.qkv_bias, slot * 128 + dlo, xl);
-            qkv_bias_add<4>(a.qkv_bias, slot * 128 + dhi, xh);
-            if (rope) {
-                bf16_t* dst = slot < a.nh ? a.qf + (size_t)slot * 8192 : a.kfresh + (size_t)(slot - a.nh) * 8192;
-                bf16x4 olo, ohi;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float c = bf2f((bf16_t)c4[j]), sn = bf2f((bf16_t)s4[j]);
-                    const float bl = bfr(xl[j]), bh = bfr(xh[j]);
-                    olo[j] = (short)f2bf(bfr(bl * c) + bfr(-bh * sn));
-                    ohi[j] = (short)f2bf(bfr(bh * c) + bfr(bl * sn));
-                }
-                *(bf16x4*)(dst + rf_offset(tok, dlo)) = olo;
-                *(bf16x4*)(dst + rf_offset(tok, dhi)) = ohi;
-            } else {
-                bf16_t* dst = a.vfresh + (size_t)(slot - a.nh - a.nkv) * 8192;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dst[vf_offset(tok, dlo + j)] = f2bf(xl[j]);
-                    dst[vf_offset(tok, dhi + j)] = f2bf(xh[j]);
-                }
-            }
+            qkv_store<4>(qd, 0, tok, pr, xl, xh, 0, rt);
             if (stamp && lane == 0) stamp[2] = wall_clock64();
             return;
         }
@@ -1021,17 +990,10 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                 for (int j = 0; j < 4; ++j) {
                     const int f = 8 * gi + 4 * hh + j;
                     if (f < ra.nv[qq]) {
-                        if constexpr (W8) {                  // gate / up row scales first (the 16-bit branch below is the original code)
-                            const int feat = ra.R * bp.bx + 32 * qq + f;
-                            const float gv = bfr(g4[j] * wsc[feat]), uv = bfr(u4[j] * wsc[a.N + feat]);
-                            const float sv = bfr(gv / (1.0f + expf(-gv)));
-                            a.act_xp[(EX ? (size_t)ex * a.ex_act : (size_t)0) + xp_offset(tok, feat)] = f2bf(sv * uv);
-                        } else {
-                            const float gv = bfr(g4[j]), uv = bfr(u4[j]);
-                            const float sv = bfr(gv / (1.0f + expf(-gv)));
-                            const int feat = ra.R * bp.bx + 32 * qq + f;
-                            a.act_xp[(EX ? (size_t)ex * a.ex_act : (size_t)0) + xp_offset(tok, feat)] = f2bf(sv * uv);
-                        }
+                        const int feat = ra.R * bp.bx + 32 * qq + f;
+                        float g = g4[j], u = u4[j];
+                        if constexpr (W8) { g *= wsc[feat]; u *= wsc[a.N + feat]; }          // gate / up row scales first
+                        a.act_xp[(EX ? (size_t)ex * a.ex_act : (size_t)0) + xp_offset(tok, feat)] = swiglu_act<false>(g, u);
                     }
                 }
             }
@@ -1040,27 +1002,14 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
             const int gi = wave & 3;
             const int ps = a.pos[tok];
             if (wave < 4 && 8 * gi + 4 * hh < ra.nv[0]) {
-                const f32x4 xl4 = total4(0, gi), xh4 = total4(1, gi);
+                f32x4 xl4 = total4(0, gi), xh4 = total4(1, gi);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int f = 8 * gi + 4 * hh + j;
                     if (f < ra.nv[0]) {
-                        const int pr = ra.R * bp.bx + f, slot = pr >> 6, dlo = pr & 63, dhi = dlo + 64;
-                        float xl = xl4[j], xh = xh4[j];
-                        if constexpr (W8) { xl *= wsc[slot * 128 + dlo]; xh *= wsc[slot * 128 + dhi]; }
-                        qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
-                        qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
-                        if (slot < a.nh + a.nkv) {
-                            bf16_t* dst = slot < a.nh ? a.qf + (size_t)slot * 8192 : a.kfresh + (size_t)(slot - a.nh) * 8192;
-                            const float c = bf2f(a.rcos[(size_t)ps * 64 + dlo]), sn = bf2f(a.rsin[(size_t)ps * 64 + dlo]);
-                            const float bl = bfr(xl), bh = bfr(xh);
-                            dst[rf_offset(tok, dlo)] = f2bf(bfr(bl * c) + bfr(-bh * sn));
-                            dst[rf_offset(tok, dhi)] = f2bf(bfr(bh * c) + bfr(bl * sn));
-                        } else {
-                            bf16_t* dst = a.vfresh + (size_t)(slot - a.nh - a.nkv) * 8192;
-                            dst[vf_offset(tok, dlo)] = f2bf(xl);
-                            dst[vf_offset(tok, dhi)] = f2bf(xh);
-                        }
+                        const int pr = ra.R * bp.bx + f;
+                        if constexpr (W8) { xl4[j] *= wsc[(pr >> 6) * 128 + (pr & 63)]; xh4[j] *= wsc[(pr >> 6) * 128 + (pr & 63) + 64]; }
+                        qkv_store<1>(qkv_dst(a, false), 0, tok, pr, xl4, xh4, j, ps);
                     }
                 }
             }
@@ -1078,15 +1027,12 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
                             const bf16_t hv = f2bf(t4[j]);
                             const int idx = ra.R * bp.bx + 32 * rb + f;
                             if (a.logits) a.logits[(size_t)tok * a.N + idx] = hv;
-                            const float v = bf2f(hv);
-                            if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
+                            argmax_better(bf2f(hv), idx, best, bidx);
                         }
                     }
                 }
             }
-            float ob = __shfl_xor(best, 32, 64);
-            int oi = __shfl_xor(bidx, 32, 64);
-            if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+            argmax_merge_halves(best, bidx);
             if (hh == 0) {
                 // park the wave's candidate of this token: [wave][64] pairs behind the reduction buffer (lk_gemm64r_logits adds
                 // LA_CAND_LDS bytes of dynamic LDS); ONE candidate per (workgroup, token) leaves the kernel (round 2: one per wave)
@@ -1104,9 +1050,7 @@ __device__ __forceinline__ void gemm64r_body(const bf16_t* __restrict__ wp_s, co
             float bv = -INFINITY; int bi = 0x7fffffff;
 #pragma unroll
             for (int w = 0; w < NW; ++w) {
-                const float v = cl[(w * LA_TB + lane) * 2];
-                const int i = ((const int*)cl)[(w * LA_TB + lane) * 2 + 1];
-                if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+                argmax_better(cl[(w * LA_TB + lane) * 2], ((const int*)cl)[(w * LA_TB + lane) * 2 + 1], bv, bi);
             }
             a.cand_val[(size_t)bp.bx * LA_TB + lane] = bv;
             a.cand_idx[(size_t)bp.bx * LA_TB + lane] = bi;
@@ -1174,22 +1118,15 @@ __global__ __launch_bounds__(256) void k_argmax_finalize(const float* __restrict
     float best = -INFINITY;
     int bidx = 0x7fffffff;
     for (int i = threadIdx.x; i < n_tiles; i += 256) {
-        float v = cv[(size_t)i * LA_TB + t];
-        int idx = ci[(size_t)i * LA_TB + t];
-        if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
+        argmax_better(cv[(size_t)i * LA_TB + t], ci[(size_t)i * LA_TB + t], best, bidx);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        float ob = __shfl_xor(best, o, 64);
-        int oi = __shfl_xor(bidx, o, 64);
-        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
-    }
+    for (int o = 32; o > 0; o >>= 1) argmax_merge_xor(best, bidx, o);
     if (lane == 0) { sv[wave] = best; si[wave] = bidx; }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bidx)) { best = sv[w]; bidx = si[w]; }
+        for (int w = 1; w < 4; ++w) argmax_better(sv[w], si[w], best, bidx);
         out[t] = bidx;
     }
 }
@@ -1313,12 +1250,9 @@ __global__ __launch_bounds__(256) void k_qkv_post(const float* __restrict__ slab
             bf16x8 o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                float x = bf2f((bf16_t)xv[e]);
-                float xr = bf2f((bf16_t)xq[e]);
+                float xr = bf2f((bf16_t)xq[e]);          // the values in LDS are rounded already: the rotate-half partner, negated for the low half
                 if (p < 8) xr = -xr;
-                float a = bfr(x * bf2f((bf16_t)cs[j][e]));
-                float b = bfr(xr * bf2f((bf16_t)sn[j][e]));
-                o[e] = (short)f2bf(a + b);
+                o[e] = (short)rope_half(bf2f((bf16_t)xv[e]), xr, bf2f((bf16_t)cs[j][e]), bf2f((bf16_t)sn[j][e]));
             }
             *(bf16x8*)(dst + rf_offset(t, d0)) = o;
         }
@@ -1787,17 +1721,13 @@ __global__ __launch_bounds__(1024) void k_step_tail(const float* __restrict__ cv
             ii[k] = ci[(size_t)ic * LA_TB + tok];
         }
 #pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if (vv[k] > best || (vv[k] == best && ii[k] < bidx)) { best = vv[k]; bidx = ii[k]; }
+        for (int k = 0; k < 16; ++k) argmax_better(vv[k], ii[k], best, bidx);
     }
     sv[part][tok] = best; si[part][tok] = bidx;
     __syncthreads();
     if (part == 0) {
 #pragma unroll
-        for (int p = 1; p < 16; ++p) {
-            const float v = sv[p][tok]; const int idx = si[p][tok];
-            if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
-        }
+        for (int p = 1; p < 16; ++p) argmax_better(sv[p][tok], si[p][tok], best, bidx);
         state[LA_ST_ARGMAX + tok] = bidx;
         accept_walk(tok, bidx, ids, rowmask, state);
     }

@@ -16,6 +16,7 @@
 #include "la_common.h"
 #include "la_mblock.h"
 #include "la_knobs.h"
+#include "la_epilogue.h"
 #include "la_mb_forms.h"      // MB_SLAB / MB_SWIGLU / MB_QKV / MB_LOGITS, the table of GEMM forms and its selector
 
 #define LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -109,10 +110,8 @@ __device__ __forceinline__ void mb_epilogue_block(const MbArgs& a, const f32x4* 
                 for (int j = 0; j < 4; ++j) {
                     const int f = 8 * gi + 4 * hh + j;
                     if (f < a.nv[rg]) {
-                        const float gv = bfr(g4[j]), uv = bfr(u4[j]);
-                        const float sv = bfr(gv / (1.0f + expf(-gv)));
                         const int feat = (NREG == 1 && a.gu_interleaved) ? (2 * blockIdx.x + qq) * 32 + f : a.R * (NREG * blockIdx.x + region) + 32 * qq + f;
-                        a.act_xp[o_off + (size_t)blk * 64 * a.N + xp_offset(tok, feat)] = f2bf(sv * uv);
+                        a.act_xp[o_off + (size_t)blk * 64 * a.N + xp_offset(tok, feat)] = swiglu_act<false>(g4[j], u4[j]);
                     }
                 }
             }
@@ -123,30 +122,11 @@ __device__ __forceinline__ void mb_epilogue_block(const MbArgs& a, const f32x4* 
         const int tb = wave >> 2, gi = wave & 3;
         const int tok = tb * 32 + tl;
         if (8 * gi + 4 * hh < a.nv[0]) {
-            const f32x4 xl4 = total4(0, tb, gi), xh4 = total4(1, tb, gi);
+            f32x4 xl4 = total4(0, tb, gi), xh4 = total4(1, tb, gi);
             const int ps = a.pos[blk * 64 + tok];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int f = 8 * gi + 4 * hh + j;
-                if (f < a.nv[0]) {
-                    const int prr = a.R * blockIdx.x + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
-                    float xl = xl4[j], xh = xh4[j];
-                    qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
-                    qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
-                    if (slot < a.nh + a.nkv) {
-                        bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
-                                                  : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
-                        const float cc = bf2f(a.rcos[(size_t)ps * 64 + dlo]), sn = bf2f(a.rsin[(size_t)ps * 64 + dlo]);
-                        const float bl = bfr(xl), bh = bfr(xh);
-                        dst[rf_offset(tok, dlo)] = f2bf(bfr(bl * cc) + bfr(-bh * sn));
-                        dst[rf_offset(tok, dhi)] = f2bf(bfr(bh * cc) + bfr(bl * sn));
-                    } else {
-                        bf16_t* dst = a.vfresh + ((size_t)blk * a.nkv + (slot - a.nh - a.nkv)) * 8192;
-                        dst[vf_offset(tok, dlo)] = f2bf(xl);
-                        dst[vf_offset(tok, dhi)] = f2bf(xh);
-                    }
-                }
-            }
+            for (int j = 0; j < 4; ++j)
+                if (8 * gi + 4 * hh + j < a.nv[0]) qkv_store<1>(qkv_dst(a, true), blk, tok, a.R * blockIdx.x + 8 * gi + 4 * hh + j, xl4, xh4, j, ps);
         }
     } else {
         static_assert(EPI != MB_LOGITS || RBV == 4, "logits layout");
@@ -166,15 +146,12 @@ __device__ __forceinline__ void mb_epilogue_block(const MbArgs& a, const f32x4* 
                         const bf16_t hv = f2bf(t4[j]);
                         const int idx = a.R * blockIdx.x + 32 * rq + f;
                         if (a.logits) a.logits[((size_t)blk * 64 + tok) * a.N + idx] = hv;
-                        const float v = bf2f(hv);
-                        if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
+                        argmax_better(bf2f(hv), idx, best, bidx);
                     }
                 }
             }
         }
-        float ob = __shfl_xor(best, 32, 64);
-        int oi = __shfl_xor(bidx, 32, 64);
-        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+        argmax_merge_halves(best, bidx);
         if (hh == 0) {
             const size_t slot = ((size_t)blk * gridDim.x + blockIdx.x) * 4 + rq;
             a.cand_val[slot * 64 + tok] = best;
@@ -399,10 +376,6 @@ __global__ __launch_bounds__(512, (DW == 4 ? 4 : 1)) void k_gemm_mb(MbArgs a) {
 // Measured anatomy (gate/up, 512 rows, profiles/r02_mblock_wide_parts.txt): MFMA issue floor 68 us at the 2.0 PFLOP/s the
 // chip sustains, DMA-only loop 67 us (x from L2 and weights from HBM share the CU's in-order vector-memory path).
 // ---------------------------------------------------------------------------------------------------------------
-// float -> bf16 on the gfx950 converter (v_cvt_pk_bf16_f32: round-to-nearest-even like f2bf, one instruction instead of six)
-__device__ __forceinline__ bf16_t f2bf_hw(float f) { return f2bf(f); }
-__device__ __forceinline__ float bfr_hw(float f) { return bf2f(f2bf_hw(f)); }
-
 template <int N> __device__ __forceinline__ void vm_wait() {
     static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
@@ -417,6 +390,21 @@ __device__ __forceinline__ void dma_piece(__amdgpu_buffer_rsrc_t rs, char* d, un
 }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t dma_rsrc(const void* p) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, 0x7ffffff0, 0x00020000);
+}
+
+// QKV epilogue of one {lo, hi} accumulator tile pair of k_gemm_fat (k_gemm_wide holds the same walk inline, see there): lane (tok, hh)
+// holds rows f = 8 (i / 4) + 4 hh + i % 4 of the workgroup region's R RoPE pairs.  RV = consecutive rows per store: 4 (R % 4 == 0),
+// 2 (R even), 1 (any R).
+template <int RV>
+__device__ __forceinline__ void qkv_tile(const MbArgs& a, f32x16 lo, f32x16 hi, int region, int blk, int tok, int hh) {
+    const int ps = a.pos[blk * 64 + tok];
+    const QkvDst qd = qkv_dst(a, true);
+#pragma unroll
+    for (int i = 0; i < 16; i += RV) {
+        if (RV > 1 && 8 * (i >> 2) >= a.nv[0]) break;                  // wave-uniform: no valid row in this register group
+        const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
+        if (f < a.nv[0]) qkv_store<RV>(qd, blk, tok, a.R * region + f, lo, hi, i, ps);
+    }
 }
 
 template <int RBV, int TW, int NRG = 4> struct WideGeom {
@@ -720,14 +708,14 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
             for (int i = 0; i < 16; ++i) {
                 if (8 * (i >> 2) >= nvg) break;                        // wave-uniform: no valid row in this register group
                 const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
-                const float gv = bfr_hw(acc[0][t][i]), uv = bfr_hw(acc[1][t][i]);
-                // silu in fast fp32 (v_exp_f32 + v_rcp_f32, ~1 ulp each): the result is rounded to bf16 right away, and the
-                // libm / IEEE-division forms cost ~60 VALU instructions per element — 64 elements per lane at 512 rows
-                const float sv = bfr_hw(gv * __builtin_amdgcn_rcpf(1.0f + __expf(-gv)));
-                const bf16_t o = f2bf_hw(sv * uv);
+                const bf16_t o = swiglu_act<true>(acc[0][t][i], acc[1][t][i]);        // the fast SiLU: 64 elements per lane at 512 rows
                 if (f < nvg) tile[trow * sw_stride + c0 + f] = o;
             }
         } else if constexpr (EPI == MB_QKV) {
+            // Kept inline, not qkv_tile<RV> (which is this code, through la_epilogue.h): in the fp16 build the compiler narrows the RoPE
+            // products and their sum to half arithmetic and contracts them into one v_fma_f16, and WHICH product stays a rounded v_mul_f16
+            // follows the shape of the surrounding code; through qkv_tile this kernel's fp16 results moved off the recorded ones
+            // (tests/test_gpu_epilogue_digests.py, forms_fp16) while every other kernel's stayed.
             // RoPE in bf16 arithmetic (apply_rotary_pos_emb, modeling_llama.py:154-169); tile 0 = lo halves, tile 1 = hi halves
             const int ps = a.pos[blk * 64 + tok];
             const int region = blockIdx.x * (RBV / 2) + rg;      // RBV = 4 (paired form): row group rg holds the {lo, hi} blocks of region 2 x + rg
@@ -752,9 +740,9 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                             for (int e = 0; e < 4; ++e) {
                                 const uint32_t cw = e < 2 ? c4.x : c4.y, sw = e < 2 ? s4.x : s4.y;
                                 const float cc = bf2f((bf16_t)(cw >> (16 * (e & 1)))), sn = bf2f((bf16_t)(sw >> (16 * (e & 1))));
-                                const float bl = bfr_hw(acc[0][t][i + e]), bh = bfr_hw(acc[1][t][i + e]);
-                                const uint32_t lo16 = (uint32_t)f2bf_hw(bfr_hw(bl * cc) + bfr_hw(-bh * sn)) << (16 * (e & 1));
-                                const uint32_t hi16 = (uint32_t)f2bf_hw(bfr_hw(bh * cc) + bfr_hw(bl * sn)) << (16 * (e & 1));
+                                const float bl = bfr(acc[0][t][i + e]), bh = bfr(acc[1][t][i + e]);
+                                const uint32_t lo16 = (uint32_t)f2bf(bfr(bl * cc) + bfr(-bh * sn)) << (16 * (e & 1));
+                                const uint32_t hi16 = (uint32_t)f2bf(bfr(bh * cc) + bfr(bl * sn)) << (16 * (e & 1));
                                 if (e < 2) { olo.x |= lo16; ohi.x |= hi16; } else { olo.y |= lo16; ohi.y |= hi16; }
                             }
                             *(uint2*)(dst + rf_offset(tok, dlo)) = olo;
@@ -763,8 +751,8 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                             bf16_t* dst = a.vfresh + ((size_t)blk * a.nkv + (slot - a.nh - a.nkv)) * 8192;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
-                                dst[vf_offset(tok, dlo + e)] = f2bf_hw(acc[0][t][i + e]);
-                                dst[vf_offset(tok, dhi + e)] = f2bf_hw(acc[1][t][i + e]);
+                                dst[vf_offset(tok, dlo + e)] = f2bf(acc[0][t][i + e]);
+                                dst[vf_offset(tok, dhi + e)] = f2bf(acc[1][t][i + e]);
                             }
                         }
                     }
@@ -787,9 +775,9 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
 #pragma unroll
                             for (int e = 0; e < 2; ++e) {
                                 const float cc = bf2f((bf16_t)(c2 >> (16 * e))), sn = bf2f((bf16_t)(s2 >> (16 * e)));
-                                const float bl = bfr_hw(acc[0][t][i + e]), bh = bfr_hw(acc[1][t][i + e]);
-                                olo |= (uint32_t)f2bf_hw(bfr_hw(bl * cc) + bfr_hw(-bh * sn)) << (16 * e);
-                                ohi |= (uint32_t)f2bf_hw(bfr_hw(bh * cc) + bfr_hw(bl * sn)) << (16 * e);
+                                const float bl = bfr(acc[0][t][i + e]), bh = bfr(acc[1][t][i + e]);
+                                olo |= (uint32_t)f2bf(bfr(bl * cc) + bfr(-bh * sn)) << (16 * e);
+                                ohi |= (uint32_t)f2bf(bfr(bh * cc) + bfr(bl * sn)) << (16 * e);
                             }
                             *(uint32_t*)(dst + rf_offset(tok, dlo)) = olo;
                             *(uint32_t*)(dst + rf_offset(tok, dhi)) = ohi;
@@ -797,8 +785,8 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                             bf16_t* dst = a.vfresh + ((size_t)blk * a.nkv + (slot - a.nh - a.nkv)) * 8192;
 #pragma unroll
                             for (int e = 0; e < 2; ++e) {
-                                dst[vf_offset(tok, dlo + e)] = f2bf_hw(acc[0][t][i + e]);
-                                dst[vf_offset(tok, dhi + e)] = f2bf_hw(acc[1][t][i + e]);
+                                dst[vf_offset(tok, dlo + e)] = f2bf(acc[0][t][i + e]);
+                                dst[vf_offset(tok, dhi + e)] = f2bf(acc[1][t][i + e]);
                             }
                         }
                     }
@@ -816,13 +804,13 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                             bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
                                                       : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
                             const float cc = bf2f(a.rcos[(size_t)ps * 64 + dlo]), sn = bf2f(a.rsin[(size_t)ps * 64 + dlo]);
-                            const float bl = bfr_hw(xl), bh = bfr_hw(xh);
-                            dst[rf_offset(tok, dlo)] = f2bf_hw(bfr_hw(bl * cc) + bfr_hw(-bh * sn));
-                            dst[rf_offset(tok, dhi)] = f2bf_hw(bfr_hw(bh * cc) + bfr_hw(bl * sn));
+                            const float bl = bfr(xl), bh = bfr(xh);
+                            dst[rf_offset(tok, dlo)] = f2bf(bfr(bl * cc) + bfr(-bh * sn));
+                            dst[rf_offset(tok, dhi)] = f2bf(bfr(bh * cc) + bfr(bl * sn));
                         } else {
                             bf16_t* dst = a.vfresh + ((size_t)blk * a.nkv + (slot - a.nh - a.nkv)) * 8192;
-                            dst[vf_offset(tok, dlo)] = f2bf_hw(xl);
-                            dst[vf_offset(tok, dhi)] = f2bf_hw(xh);
+                            dst[vf_offset(tok, dlo)] = f2bf(xl);
+                            dst[vf_offset(tok, dhi)] = f2bf(xh);
                         }
                     }
                 }
@@ -841,13 +829,10 @@ __global__ __launch_bounds__(512) void k_gemm_wide(MbArgs a) {
                         const bf16_t hv = f2bf(acc[r][t][i]);
                         const int idx = a.R * blockIdx.x + 32 * rq + f;
                         if (a.logits) a.logits[((size_t)blk * 64 + tok) * a.N + idx] = hv;
-                        const float v = bf2f(hv);
-                        if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
+                        argmax_better(bf2f(hv), idx, best, bidx);
                     }
                 }
-                float ob = __shfl_xor(best, 32, 64);
-                int oi = __shfl_xor(bidx, 32, 64);
-                if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+                argmax_merge_halves(best, bidx);
                 if (hh == 0) {
                     const size_t slot = ((size_t)blk * gridDim.x + blockIdx.x) * 4 + rq;
                     a.cand_val[slot * 64 + tok] = best;
@@ -908,106 +893,6 @@ template <int RBV, int TW, int RPW_ = 4> struct FatGeom {
     static constexpr int BLOCKS = NTBP / 2;
     static_assert((RBV == 8 || RBV == 4 || RBV == 2) && RBV % RPW == 0 && STAGE % NW == 0 && A_STAGE % NW == 0 && NTBP % 2 == 0 && LDS <= 160 * 1024, "ring geometry");
 };
-
-// RoPE + fragment stores of one {lo, hi} accumulator pair (the QKV epilogue of k_gemm_wide, same arithmetic and rounding points:
-// apply_rotary_pos_emb, modeling_llama.py:154-169, in bf16 arithmetic; V rows pass through)
-// RV = rows a lane handles per store: 4 (R % 4 == 0: 8-byte table loads and fragment stores), 2 (R even: 4-byte), 1 (any R)
-template <int RV>
-__device__ __forceinline__ void fat_qkv_tile(const MbArgs& a, f32x16 lo, f32x16 hi, int region, int blk, int tok, int hh) {
-    const int ps = a.pos[blk * 64 + tok];
-    if constexpr (RV == 4) {
-#pragma unroll
-        for (int i = 0; i < 16; i += 4) {
-            if (8 * (i >> 2) >= a.nv[0]) break;
-            const int f = 8 * (i >> 2) + 4 * hh;
-            if (f < a.nv[0]) {
-                const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
-                qkv_bias_add<4>(a.qkv_bias, slot * 128 + dlo, lo, i);
-                qkv_bias_add<4>(a.qkv_bias, slot * 128 + dhi, hi, i);
-                if (slot < a.nh + a.nkv) {
-                    bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
-                                              : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
-                    const uint2 c4 = *(const uint2*)(a.rcos + (size_t)ps * 64 + dlo), s4 = *(const uint2*)(a.rsin + (size_t)ps * 64 + dlo);
-                    uint2 olo = {0u, 0u}, ohi = {0u, 0u};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const uint32_t cw = e < 2 ? c4.x : c4.y, sw = e < 2 ? s4.x : s4.y;
-                        const float cc = bf2f((bf16_t)(cw >> (16 * (e & 1)))), sn = bf2f((bf16_t)(sw >> (16 * (e & 1))));
-                        const float bl = bfr_hw(lo[i + e]), bh = bfr_hw(hi[i + e]);
-                        const uint32_t lo16 = (uint32_t)f2bf_hw(bfr_hw(bl * cc) + bfr_hw(-bh * sn)) << (16 * (e & 1));
-                        const uint32_t hi16 = (uint32_t)f2bf_hw(bfr_hw(bh * cc) + bfr_hw(bl * sn)) << (16 * (e & 1));
-                        if (e < 2) { olo.x |= lo16; ohi.x |= hi16; } else { olo.y |= lo16; ohi.y |= hi16; }
-                    }
-                    *(uint2*)(dst + rf_offset(tok, dlo)) = olo;
-                    *(uint2*)(dst + rf_offset(tok, dhi)) = ohi;
-                } else {
-                    bf16_t* dst = a.vfresh + ((size_t)blk * a.nkv + (slot - a.nh - a.nkv)) * 8192;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        dst[vf_offset(tok, dlo + e)] = f2bf_hw(lo[i + e]);
-                        dst[vf_offset(tok, dhi + e)] = f2bf_hw(hi[i + e]);
-                    }
-                }
-            }
-        }
-    } else if constexpr (RV == 2) {
-#pragma unroll
-        for (int i = 0; i < 16; i += 2) {
-            if (8 * (i >> 2) >= a.nv[0]) break;
-            const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
-            if (f < a.nv[0]) {
-                const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
-                qkv_bias_add<2>(a.qkv_bias, slot * 128 + dlo, lo, i);
-                qkv_bias_add<2>(a.qkv_bias, slot * 128 + dhi, hi, i);
-                if (slot < a.nh + a.nkv) {
-                    bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
-                                              : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
-                    const uint32_t c2 = *(const uint32_t*)(a.rcos + (size_t)ps * 64 + dlo), s2 = *(const uint32_t*)(a.rsin + (size_t)ps * 64 + dlo);
-                    uint32_t olo = 0, ohi = 0;
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const float cc = bf2f((bf16_t)(c2 >> (16 * e))), sn = bf2f((bf16_t)(s2 >> (16 * e)));
-                        const float bl = bfr_hw(lo[i + e]), bh = bfr_hw(hi[i + e]);
-                        olo |= (uint32_t)f2bf_hw(bfr_hw(bl * cc) + bfr_hw(-bh * sn)) << (16 * e);
-                        ohi |= (uint32_t)f2bf_hw(bfr_hw(bh * cc) + bfr_hw(bl * sn)) << (16 * e);
-                    }
-                    *(uint32_t*)(dst + rf_offset(tok, dlo)) = olo;
-                    *(uint32_t*)(dst + rf_offset(tok, dhi)) = ohi;
-                } else {
-                    bf16_t* dst = a.vfresh + ((size_t)blk * a.nkv + (slot - a.nh - a.nkv)) * 8192;
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        dst[vf_offset(tok, dlo + e)] = f2bf_hw(lo[i + e]);
-                        dst[vf_offset(tok, dhi + e)] = f2bf_hw(hi[i + e]);
-                    }
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
-            if (f < a.nv[0]) {
-                const int prr = a.R * region + f, slot = prr >> 6, dlo = prr & 63, dhi = dlo + 64;
-                float xl = lo[i], xh = hi[i];
-                qkv_bias_add<1>(a.qkv_bias, slot * 128 + dlo, xl);
-                qkv_bias_add<1>(a.qkv_bias, slot * 128 + dhi, xh);
-                if (slot < a.nh + a.nkv) {
-                    bf16_t* dst = slot < a.nh ? a.qf + ((size_t)blk * a.nh + slot) * 8192
-                                              : a.kfresh + ((size_t)blk * a.nkv + (slot - a.nh)) * 8192;
-                    const float cc = bf2f(a.rcos[(size_t)ps * 64 + dlo]), sn = bf2f(a.rsin[(size_t)ps * 64 + dlo]);
-                    const float bl = bfr_hw(xl), bh = bfr_hw(xh);
-                    dst[rf_offset(tok, dlo)] = f2bf_hw(bfr_hw(bl * cc) + bfr_hw(-bh * sn));
-                    dst[rf_offset(tok, dhi)] = f2bf_hw(bfr_hw(bh * cc) + bfr_hw(bl * sn));
-                } else {
-                    bf16_t* dst = a.vfresh + ((size_t)blk * a.nkv + (slot - a.nh - a.nkv)) * 8192;
-                    dst[vf_offset(tok, dlo)] = f2bf_hw(xl);
-                    dst[vf_offset(tok, dhi)] = f2bf_hw(xh);
-                }
-            }
-        }
-    }
-}
 
 // STG = 1 (round 5, second form): the operands reach LDS through REGISTERS (buffer_load_dwordx4 -> VGPR -> ds_write_b128) instead of LDS-DMA.
 //   What the DMA form pays: an LDS-DMA piece blocks its wave's issue for ~60-185 cycles (MI355X_MICROARCH.md price list), and with one wave per
@@ -1336,7 +1221,7 @@ __global__ __launch_bounds__(256) void k_gemm_fat(MbArgs a) {
             if (blk >= a.nblk) continue;
 #pragma unroll
             for (int j = 0; j < RPW / 2; ++j)            // region (RBV / 2) x + j = row-blocks {2 j, 2 j + 1} = its {lo, hi} halves
-                fat_qkv_tile<RV>(a, acc[2 * j][t], acc[2 * j + 1][t], bx * (RBV / 2) + (RPW / 2) * rg + j, blk, tok, hh);
+                qkv_tile<RV>(a, acc[2 * j][t], acc[2 * j + 1][t], bx * (RBV / 2) + (RPW / 2) * rg + j, blk, tok, hh);
         }
     } else {
         // ---- SwiGLU epilogue, as k_gemm_wide<8, TW, MB_SWIGLU>: act = bf16(silu(bf16(g)) * bf16(u)) parked as tile[token][sh + feature -
@@ -1360,9 +1245,7 @@ __global__ __launch_bounds__(256) void k_gemm_fat(MbArgs a) {
                 for (int i = 0; i < 16; ++i) {
                     if (8 * (i >> 2) >= nvg) break;
                     const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
-                    const float gv = bfr_hw(acc[q][t][i]), uv = bfr_hw(acc[q + 2][t][i]);
-                    const float sv = bfr_hw(gv * __builtin_amdgcn_rcpf(1.0f + __expf(-gv)));
-                    const bf16_t o = f2bf_hw(sv * uv);
+                    const bf16_t o = swiglu_act<true>(acc[q][t][i], acc[q + 2][t][i]);
                     if (f < nvg) tile[trow * sw_stride + c0 + f] = o;
                 }
             }
@@ -1556,9 +1439,7 @@ __global__ __launch_bounds__(256) void k_gemm_fatd(MbArgs a) {
         for (int i = 0; i < 16; ++i) {
             if (8 * (i >> 2) >= nvg) break;
             const int f = 8 * (i >> 2) + 4 * hh + (i & 3);
-            const float gv = bfr_hw(acc[0][t][i]), uv = bfr_hw(acc[1][t][i]);
-            const float sv = bfr_hw(gv * __builtin_amdgcn_rcpf(1.0f + __expf(-gv)));
-            const bf16_t o = f2bf_hw(sv * uv);
+            const bf16_t o = swiglu_act<true>(acc[0][t][i], acc[1][t][i]);
             if (f < nvg) tile[trow * sw_stride + c0 + f] = o;
         }
     }
@@ -2439,22 +2320,15 @@ __global__ __launch_bounds__(256) void k_argmax_mb(const float* __restrict__ cv,
     float best = -INFINITY;
     int bidx = 0x7fffffff;
     for (int i = threadIdx.x; i < n_tiles; i += 256) {
-        const float v = cvb[(size_t)i * 64 + t];
-        const int idx = cib[(size_t)i * 64 + t];
-        if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
+        argmax_better(cvb[(size_t)i * 64 + t], cib[(size_t)i * 64 + t], best, bidx);
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bidx, o, 64);
-        if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
-    }
+    for (int o = 32; o > 0; o >>= 1) argmax_merge_xor(best, bidx, o);
     if (lane == 0) { sv[wave] = best; si[wave] = bidx; }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bidx)) { best = sv[w]; bidx = si[w]; }
+        for (int w = 1; w < 4; ++w) argmax_better(sv[w], si[w], best, bidx);
         out[blk * 64 + t] = bidx;
     }
 }

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(1024) void k_pen_argmax(const PenArgs a) {
             for (int e = 0; e < 8; ++e) {
                 const bf16_t s = (bf16_t)x[k][e];
                 const float v = ((member >> e) & 1u) ? pen_value(s, p) : bf2f(s);
-                pen_better(v, c * 8 + e, best, bidx);
+                argmax_better(v, c * 8 + e, best, bidx);
             }
         }
     }
@@ -71,13 +71,13 @@ __global__ __launch_bounds__(1024) void k_pen_argmax(const PenArgs a) {
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bidx, o, 64);
-        pen_better(ob, oi, best, bidx);
+        argmax_better(ob, oi, best, bidx);
     }
     if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = bidx; }
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-        for (int w = 1; w < 16; ++w) pen_better(sv[w], si[w], best, bidx);
+        for (int w = 1; w < 16; ++w) argmax_better(sv[w], si[w], best, bidx);
         a.out[r.row] = bidx;
     }
 }

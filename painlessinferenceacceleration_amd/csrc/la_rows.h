@@ -12,10 +12,6 @@ __device__ __forceinline__ float pen_value(bf16_t x, float p) {
     return bfr(v < 0.f ? v * p : v / p);
 }
 
-__device__ __forceinline__ void pen_better(float v, int idx, float& best, int& bidx) {
-    if (v > best || (v == best && idx < bidx)) { best = v; bidx = idx; }
-}
-
 // Which row of which slot this workgroup serves, and whether the step reads its argmax at all.
 struct PenRow {
     bool live;

@@ -263,7 +263,7 @@ __global__ __launch_bounds__(SAMP_THREADS) void k_sample_rows(const SampArgs a) 
                 ++kept;
                 const float u = ((float)(w[e] >> 9) + 0.5f) * 1.1920928955078125e-07f;
                 const float g = -logf(-logf(u));
-                pen_better(samp_val(key) / T + g, c * 8 + half * 4 + e, best, bidx);
+                argmax_better(samp_val(key) / T + g, c * 8 + half * 4 + e, best, bidx);
             }
         }
     });
@@ -271,14 +271,14 @@ __global__ __launch_bounds__(SAMP_THREADS) void k_sample_rows(const SampArgs a) 
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bidx, o, 64);
-        pen_better(ob, oi, best, bidx);
+        argmax_better(ob, oi, best, bidx);
         kept += __shfl_xor(kept, o, 64);
     }
     if ((tid & 63) == 0) { redv[tid >> 6] = best; redi[tid >> 6] = bidx; atomicAdd(&sel[2], kept); }
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-        for (int w = 1; w < SAMP_THREADS / 64; ++w) pen_better(redv[w], redi[w], best, bidx);
+        for (int w = 1; w < SAMP_THREADS / 64; ++w) argmax_better(redv[w], redi[w], best, bidx);
         a.p.out[r.row] = bidx < vocab ? bidx : 0;
         if (a.info) {
             int* inf = a.info + (size_t)r.row * 4;

@@ -31,8 +31,16 @@ FORM_CASES = [
     ('WIDE<4,4,LOGITS,0,3,0,0>', 3, 7, 256, (256, 0)),
 ]
 
+# QKV launches whose plan gives a workgroup an ODD number of RoPE pairs (R = 5): the one-row-per-store paths of the multi-block QKV
+# epilogues, which no product shape reaches (R is a multiple of 4 at every model shape).  tests/test_gpu_epilogue_digests.py pins them.
+ODD_R_CASES = [
+    ('MB<2,2,QKV,0,8,0,0>', 2, 1, 272, (3, 1, 64)),
+    ('WIDE<4,1,QKV,0,2,0,0>', 2, 3, 272, (3, 1, 64)),
+    ('WIDE<4,2,QKV,0,2,0,0>', 2, 5, 272, (11, 2, 192)),
+]
 
-def selector_input(kind, nblk, K, shape):
+
+def selector_input(kind, nblk, K, shape, bias=0):
     """The MbFormIn tuple lk_mb_gemm derives from a la_mb_gemm call (field order of tests/test_mb_forms_cpu.py FIELDS)."""
     if kind == 0:
         N, n_wg, R, planned = shape, shape // 64, 0, 0
@@ -45,4 +53,4 @@ def selector_input(kind, nblk, K, shape):
         per = 64 if kind == 1 else 128
         planned = int(n_wg > 0)
         n_wg, R = (n_wg, N // n_wg) if planned else (N // per, per)
-    return (kind, nblk, n_wg, 1, K // 16, N, R, planned, int(kind == 1 and not planned), 0, 0, 0)
+    return (kind, nblk, n_wg, 1, K // 16, N, R, planned, int(kind == 1 and not planned), 0, 0, bias)

@@ -184,3 +184,15 @@ def test_gpu_form_cases_select_the_forms_they_name(programs, tmp_path):
     assert got == [c[0] for c in FORM_CASES]
     table = [l.split()[1:] for l in _lines(programs[0]) if l.startswith('table ')][0]
     assert set(got) == {n for n in table if not (n.startswith('MB<') and n.split(',')[3] == '1')}
+
+
+@pytest.mark.parametrize('bias', [0, 1])
+def test_odd_r_qkv_cases_select_the_one_row_per_store_forms(programs, tmp_path, bias):
+    """tests/mb_form_cases.py ODD_R_CASES (launched by tests/test_gpu_epilogue_digests.py): R = 5 pairs per workgroup, with and without a
+    bias, selects the three kernels that hold a one-row-per-store QKV epilogue — k_gemm_mb, and k_gemm_wide unpaired and paired."""
+    from tests.mb_form_cases import ODD_R_CASES, selector_input
+    p = tmp_path / 'odd_r.txt'
+    p.write_text(''.join(' '.join(str(v) for v in selector_input(*c[1:], bias=bias)) + '\n' for c in ODD_R_CASES))
+    for c in ODD_R_CASES:
+        assert selector_input(*c[1:])[FIELDS.index('R')] == 5
+    assert [l.split()[0] for l in _lines(programs[0], 'answer', str(p))] == [c[0] for c in ODD_R_CASES]
