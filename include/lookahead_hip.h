@@ -383,6 +383,18 @@ int la_qkv_post(void* stream, const float* d_slabs, int n_slabs, int n_heads, in
 int la_qkv_post_bias(void* stream, const float* d_slabs, int n_slabs, int n_heads, int n_kv_heads,
                      const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin,
                      void* d_qf, void* d_kfresh, void* d_vfresh, const void* d_bias);
+/* Per-head q / k RMSNorm + RoPE (Qwen3: q_norm / k_norm over the 128 features of every head, applied to the q_proj / k_proj output
+ * before apply_rotary_pos_emb), in place on the QF fragments and the FRESH KF fragments a QKV launch has just written with IDENTITY
+ * RoPE tables (cos = 1, sin = 0: the fragments then hold the rounded nn.Linear output): 8192 elements per head and 64-row block,
+ * block b, head s at (b * heads + s) * 8192.  For every (block, q or k head, token row): n = storage(f * rsqrt(mean(f^2) + eps)) with
+ * an fp32 mean of squares, y = storage(w * n) (the cast-first flavour of Qwen3RMSNorm.forward), then rotate-half RoPE of y with the
+ * real tables at d_pos[b * 64 + row] (two rounded products, one rounded sum).  V is not touched.  d_q_weight / d_k_weight: 128
+ * storage-type values each; every pointer but d_pos 16-byte aligned; nblk = 1 .. LA_MB_MAX; d_pos has nblk * 64 entries, the array the
+ * QKV launch read.  A head's 128 features are finished by two or more workgroups of every QKV launch form, so no QKV epilogue ever
+ * holds a head's sum of squares: this is a stage of its own, one launch behind the QKV launch. */
+int la_qk_norm_rope(void* stream, void* d_qf, void* d_kfresh, int nblk, int n_heads, int n_kv_heads,
+                    const void* d_q_weight, const void* d_k_weight, float eps,
+                    const int32_t* d_pos, const void* d_rope_cos, const void* d_rope_sin);
 /* Tree attention: mask-free prefix from the packed main cache + 64 fresh keys under rowmask. */
 int la_tree_attn(void* stream, const void* d_qf, const void* d_kmain, const void* d_vmain,
                  const void* d_kfresh, const void* d_vfresh, const uint64_t* d_rowmask,
@@ -470,6 +482,18 @@ typedef struct la_llama_weights {
 int64_t   la_llama_workspace_bytes(const la_llama_config* cfg);
 la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_weights* w,
                           void* d_workspace, int64_t workspace_bytes);
+/* Qwen3: la_llama_create with the per-head RMSNorm of q and k between the projection and RoPE.  Every QKV launch of a layer then runs
+ * with the identity tables and la_qk_norm_rope follows it directly, on every step entry point.  No struct above changed for it: a
+ * caller of la_llama_create gets the model without the stage, exactly as before.  Needs head_dim = 128, fuse = 0 and n_experts = 0;
+ * anything else, a missing pointer or a misaligned one is refused (NULL + la_last_error), never served without the norm. */
+typedef struct la_qk_norm_weights {
+    const void* const* q_norm;   /* host array [n_layers] of device pointers: self_attn.q_norm weight, 128 storage-type values, 16-byte aligned */
+    const void* const* k_norm;   /* ... self_attn.k_norm */
+    const void* rope_cos_id;     /* identity tables of the extent of rope_cos / rope_sin (cos = 1, sin = 0), 16-byte aligned like the real ones */
+    const void* rope_sin_id;
+} la_qk_norm_weights;
+la_llama* la_llama_create_qk_norm(const la_llama_config* cfg, const la_llama_weights* w, const la_qk_norm_weights* qk,
+                                  void* d_workspace, int64_t workspace_bytes);
 void      la_llama_destroy(la_llama* m);
 /* Reset the sequence (nkeys = 0). */
 int la_llama_reset(la_llama* m, void* stream);

@@ -7,6 +7,8 @@ Drop-in surface (reference: alipay/PainlessInferenceAcceleration, lookahead/):
     LlamaForCausalLM                       lookahead/models/llama/modeling_llama.py
     modeling_llama_batch.LlamaForCausalLM  lookahead/models/llama/modeling_llama_batch.py (bs>1, cursor batch)
     Qwen2ForCausalLM                       lookahead/models/qwen2/modeling_qwen2.py (Qwen1.5 / Qwen2 / Qwen2.5; BatchQwen2ForCausalLM: bs>1)
+    Qwen3ForCausalLM                       Qwen3 dense (transformers models/qwen3/modeling_qwen3.py; BatchQwen3ForCausalLM: bs>1): an
+                                           extension, the reference has no Qwen3 model
 All compute lives in liblookahead_hip.so (csrc/, hand-written gfx950 HIP + the native trie).
 """
 from ._lib import LIB_PATH, LookaheadHipError  # noqa: F401  (raises at import if the library is not built)
@@ -28,6 +30,9 @@ def __getattr__(name):          # torch-dependent pieces are imported lazily
     if name in ('Qwen2ForCausalLM', 'BatchQwen2ForCausalLM'):
         from . import modeling_qwen2
         return getattr(modeling_qwen2, name)
+    if name in ('Qwen3ForCausalLM', 'BatchQwen3ForCausalLM'):
+        from . import modeling_qwen3
+        return getattr(modeling_qwen3, name)
     if name in ('LookaheadPreTrainedModel',):
         from .pretrained_model import LookaheadPreTrainedModel
         return LookaheadPreTrainedModel

@@ -101,6 +101,11 @@ class LlamaWeightsC(C.Structure):
                 ("layers", C.POINTER(LlamaLayerWeightsC))]
 
 
+class QkNormWeightsC(C.Structure):
+    """la_qk_norm_weights: what la_llama_create_qk_norm takes beside the config and the weights (Qwen3)"""
+    _fields_ = [("q_norm", C.POINTER(vp)), ("k_norm", C.POINTER(vp)), ("rope_cos_id", vp), ("rope_sin_id", vp)]
+
+
 class TrieImageC(C.Structure):
     """la_trie_image: the device arrays of the trie mirror (device pointers as integers)"""
     _fields_ = [('tok', C.c_void_p), ('fo', C.c_void_p), ('fi', C.c_void_p), ('fi_stride', C.c_int64), ('n_planes', C.c_int32),
@@ -194,9 +199,11 @@ PROTOTYPES = {
     "la_resid_norm": (i32, vp, vp, vp, i32, vp, i32, f32, vp),
     "la_qkv_post": (i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp),
     "la_qkv_post_bias": (i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp),
+    "la_qk_norm_rope": (i32, vp, vp, vp, i32, i32, i32, vp, vp, f32, vp, vp, vp),
     "la_tree_attn": (i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp),
     "la_llama_workspace_bytes": (i64, C.POINTER(LlamaConfigC)),
     "la_llama_create": (vp, C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), vp, i64),
+    "la_llama_create_qk_norm": (vp, C.POINTER(LlamaConfigC), C.POINTER(LlamaWeightsC), C.POINTER(QkNormWeightsC), vp, i64),
     "la_llama_destroy": (None, vp),
     "la_llama_reset": (i32, vp, vp),
     "la_llama_step": (i32, vp, vp, vp, vp),

@@ -8,7 +8,7 @@ set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 BASEFLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -mllvm -amdgpu-kernarg-preload-count=16 ${LA_EXTRA_HIPCC_FLAGS:-}"
-SRCS_PRODUCT="la_kernels.hip la_attn1.hip la_mblock.hip la_penalty.hip la_sample.hip la_logprob.hip la_trie_dev.hip la_trie_wg.hip la_engine.cpp la_abi.cpp la_trie.cpp la_comm.cpp"
+SRCS_PRODUCT="la_kernels.hip la_attn1.hip la_mblock.hip la_penalty.hip la_sample.hip la_logprob.hip la_qknorm.hip la_trie_dev.hip la_trie_wg.hip la_engine.cpp la_abi.cpp la_trie.cpp la_comm.cpp"
 SRCS="$SRCS_PRODUCT"
 build_one() {     # out.so, object dir, extra flags, extra sources
   local OUT="$1" OBJ="$2" FLAGS="$BASEFLAGS $3" SRCS="$SRCS_PRODUCT ${4:-}"

@@ -202,6 +202,14 @@ int la_qkv_post(void* stream, const float* slabs, int n_slabs, int nh, int nkv, 
                 const void* rsin, void* qf, void* kf, void* vf) {
     return la_qkv_post_bias(stream, slabs, n_slabs, nh, nkv, pos, rcos, rsin, qf, kf, vf, nullptr);
 }
+int la_qk_norm_rope(void* stream, void* qf, void* kf, int nblk, int nh, int nkv, const void* q_weight, const void* k_weight, float eps,
+                    const int32_t* pos, const void* rcos, const void* rsin) {
+    // every vector is read with 16-byte loads
+    if (!qf || !kf || !q_weight || !k_weight || !pos || !rcos || !rsin || nblk < 1 || nblk > LA_MB_MAX || nh <= 0 || nkv <= 0 ||
+        !(eps >= 0.f) || (((uintptr_t)qf | (uintptr_t)kf | (uintptr_t)q_weight | (uintptr_t)k_weight | (uintptr_t)rcos | (uintptr_t)rsin) & 15))
+        return LA_E_ARG;
+    WRAP(lk_qk_norm_rope((hipStream_t)stream, qf, kf, nblk, nh, nkv, q_weight, k_weight, eps, pos, rcos, rsin));
+}
 int la_tree_attn(void* stream, const void* qf, const void* km, const void* vm, const void* kf, const void* vf,
                  const uint64_t* rowmask, const int32_t* d_state, int nh, int nkv, int max_keys, int nsplit,
                  float* opart, float* mpart, float* lpart, void* attn_xp) {

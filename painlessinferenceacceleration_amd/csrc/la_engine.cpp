@@ -129,6 +129,11 @@ struct la_llama {
     int lp_stride = 0;
     bool lp_on = false;
     int lp_launches = 0;
+    // per-head q / k RMSNorm stage (la_llama_create_qk_norm; la_qknorm.hip): the layers' norm weights and the identity RoPE tables the
+    // QKV launches run with while it is on
+    bool qk_norm = false;
+    std::vector<const void*> q_norm, k_norm;
+    const void *rope_cos_id = nullptr, *rope_sin_id = nullptr;
 };
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -323,6 +328,15 @@ static const char* w8_refusal(const la_llama_config* c) {
     return nullptr;
 }
 
+// The q / k norm stage (Qwen3, la_llama_create_qk_norm; la_qknorm.hip) normalises over the 128 features of a lane, and it is wired behind
+// the QKV launch of the plain step forms only; everything else is refused rather than served without the norm.  Null: supported.
+static const char* qk_norm_refusal(const la_llama_config* c) {
+    if (c->head_dim != 128) return "qk_norm needs head_dim = 128 (the norm runs over the 128 features of a head lane; padded lanes would enter the mean)";
+    if (c->fuse != 0) return "qk_norm: the fused norm / role-fused launches (fuse != 0) are not served with the q / k norm stage";
+    if (c->n_experts > 0) return "qk_norm: MoE models are not served with the q / k norm stage";
+    return nullptr;
+}
+
 static int validate(const la_llama_config* c) {
     if (!c) return LA_E_ARG;
     if (const char* why = w8_refusal(c)) { la_set_error(why); return LA_E_ARG; }
@@ -358,7 +372,7 @@ static hipError_t lp_clear(la_llama* m, hipStream_t st, int slot) {
     return hipMemsetAsync(m->lp_log + (size_t)slot * m->lp_stride, 0xff, (size_t)m->lp_stride * sizeof(float), st);
 }
 
-extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_weights* w, void* ws, int64_t ws_bytes) {
+static la_llama* create(const la_llama_config* cfg, const la_llama_weights* w, const la_qk_norm_weights* qk, void* ws, int64_t ws_bytes) {
     if (validate(cfg) != LA_OK || !w || !ws || !w->layers) { if (!w || !ws) la_set_error("null weights/workspace"); return nullptr; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -376,6 +390,19 @@ extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_
     m->w.layers = m->layers.data();
     for (int l = 0; l < cfg->n_layers; ++l)
         if ((uintptr_t)w->layers[l].qkv_bias & 7) { la_set_error("qkv_bias must be 8-byte aligned"); delete m; return nullptr; }
+    if (qk) {
+        if (const char* why = qk_norm_refusal(cfg)) { la_set_error(why); delete m; return nullptr; }
+        if (!qk->q_norm || !qk->k_norm || !qk->rope_cos_id || !qk->rope_sin_id ||
+            (((uintptr_t)qk->rope_cos_id | (uintptr_t)qk->rope_sin_id | (uintptr_t)w->rope_cos | (uintptr_t)w->rope_sin) & 15)) {
+            la_set_error("qk_norm: the weight arrays or the identity RoPE tables (rope_cos_id / rope_sin_id) are missing, or a RoPE table is not 16-byte aligned"); delete m; return nullptr;
+        }
+        for (int l = 0; l < cfg->n_layers; ++l)
+            if (!qk->q_norm[l] || !qk->k_norm[l] || (((uintptr_t)qk->q_norm[l] | (uintptr_t)qk->k_norm[l]) & 15)) { la_set_error("qk_norm: every layer needs q_norm and k_norm (128 values each), 16-byte aligned"); delete m; return nullptr; }
+        m->qk_norm = true;
+        m->q_norm.assign(qk->q_norm, qk->q_norm + cfg->n_layers);
+        m->k_norm.assign(qk->k_norm, qk->k_norm + cfg->n_layers);
+        m->rope_cos_id = qk->rope_cos_id; m->rope_sin_id = qk->rope_sin_id;
+    }
     if (cfg->weight_format == 1)
         for (int l = 0; l < cfg->n_layers; ++l) {
             const la_llama_layer_weights& L = w->layers[l];
@@ -414,6 +441,16 @@ extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_
     if (m->mb_max && lk_mb_init() != 0) { la_set_error("hipFuncSetAttribute failed for the multi-block kernels"); delete m; return nullptr; }
     if (lp_clear(m, nullptr, -1) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { la_set_error("la_llama_create: clearing the log-probability log failed"); delete m; return nullptr; }
     return m;
+}
+
+extern "C" la_llama* la_llama_create(const la_llama_config* cfg, const la_llama_weights* w, void* ws, int64_t ws_bytes) {
+    return create(cfg, w, nullptr, ws, ws_bytes);
+}
+// ... with the Qwen3 per-head q / k RMSNorm stage behind every QKV launch (la_qk_norm_rope)
+extern "C" la_llama* la_llama_create_qk_norm(const la_llama_config* cfg, const la_llama_weights* w, const la_qk_norm_weights* qk,
+                                             void* ws, int64_t ws_bytes) {
+    if (!qk) { la_set_error("la_llama_create_qk_norm: null la_qk_norm_weights"); return nullptr; }
+    return create(cfg, w, qk, ws, ws_bytes);
 }
 
 // every captured graph of the model holds the step WITH or WITHOUT each row stage (penalty, sampling, log-probabilities): switching
@@ -597,6 +634,9 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, const StepForm& f
     const int* fk = g_la_fork_pf;
     const int ring = c.kv_ring ? c.max_keys : 0;          // sliding-window ring: position p of a sequence lives in row p mod max_keys
     auto P = [&](int cls) { if (pf) pf->mark(cls); };
+    // qk_norm: the QKV launch leaves the rounded projection output (identity tables); la_qk_norm_rope behind it applies the real ones
+    const void* const qkv_cos = m->qk_norm ? m->rope_cos_id : m->w.rope_cos;
+    const void* const qkv_sin = m->qk_norm ? m->rope_sin_id : m->w.rope_sin;
     P(KC_OTHER);
     if (batch) KCHK(lk_build_tree_inputs_b(st, m->bin, m->bstate, m->pos, m->rowmask, m->ids));
     else if (g_la_split_head_tail) KCHK(lk_build_tree_inputs(st, form.zc_in ? (const int*)form.zc_in : m->in, m->state, m->pos, m->rowmask, m->ids));
@@ -634,16 +674,20 @@ static int enqueue_step(la_llama* m, hipStream_t st, Prof* pf, const StepForm& f
             // layers > 0: the input norm (residual + down-projection slabs of the previous layer) runs inside this launch
             FusedNorm fq{m->slabs, m->down_ks, m->h, L.norm1, c.hidden, c.rms_eps, cf, m->fuse_cnt + 2 * l, (m->fuse & 16) ? 1 : 0};
             KCHK(lk_gemm64r_qkv(st, L.wqkv, m->xp, c.n_heads, c.n_kv_heads, c.hidden, c.balanced_wg[0], m->pos,
-                                m->w.rope_cos, m->w.rope_sin, m->qf, kf, vf, ((m->fuse & 2) && l > 0) ? &fq : nullptr, L.qkv_bias,
+                                qkv_cos, qkv_sin, m->qf, kf, vf, ((m->fuse & 2) && l > 0) ? &fq : nullptr, L.qkv_bias,
                                 w8 ? L.wqkv_scale : nullptr));
         } else if (m->qkv_fused) {
-            KCHK(lk_gemm64_qkv(st, L.wqkv, m->xp, c.n_heads, c.n_kv_heads, c.hidden, m->pos, m->w.rope_cos, m->w.rope_sin,
+            KCHK(lk_gemm64_qkv(st, L.wqkv, m->xp, c.n_heads, c.n_kv_heads, c.hidden, m->pos, qkv_cos, qkv_sin,
                                m->qf, kf, vf, m->qkv_rb >> 8, L.qkv_bias, w8 ? L.wqkv_scale : nullptr));
         } else {
             KCHK(lk_gemm64_slab(st, L.wqkv, m->xp, m->qkv_n, c.hidden, m->qkv_rb, m->qkv_ks, m->slabs));
             P(KC_OTHER);
-            KCHK(lk_qkv_post(st, m->slabs, m->qkv_ks, c.n_heads, c.n_kv_heads, m->pos, m->w.rope_cos, m->w.rope_sin,
+            KCHK(lk_qkv_post(st, m->slabs, m->qkv_ks, c.n_heads, c.n_kv_heads, m->pos, qkv_cos, qkv_sin,
                              m->qf, kf, vf, L.qkv_bias));
+        }
+        if (m->qk_norm) {
+            P(KC_OTHER);
+            KCHK(lk_qk_norm_rope(st, m->qf, kf, 1, c.n_heads, c.n_kv_heads, m->q_norm[l], m->k_norm[l], c.rms_eps, m->pos, m->w.rope_cos, m->w.rope_sin));
         }
         P(KC_ATTN);
         if (fork && c.n_experts == 0) {
@@ -920,9 +964,12 @@ static int enqueue_mstep(la_llama* m, hipStream_t st, int nblk, bool wide = fals
         // >= 3 blocks (the wide launches): the image planned for fewer, fuller workgroups when the model carries one (cfg.qkv_mb_wg)
         const bool mbq = c.qkv_mb_wg > 0 && L.wqkv_mb && nblk >= 3;
         q.wp = mbq ? L.wqkv_mb : L.wqkv; q.n_wg = mbq ? c.qkv_mb_wg : c.balanced_wg[0];
-        q.pos = m->mb_pos; q.rcos = m->w.rope_cos; q.rsin = m->w.rope_sin; q.qf = m->mb_qf; q.kfresh = kf; q.vfresh = vf;
+        q.pos = m->mb_pos; q.qf = m->mb_qf; q.kfresh = kf; q.vfresh = vf;
+        q.rcos = m->qk_norm ? m->rope_cos_id : m->w.rope_cos; q.rsin = m->qk_norm ? m->rope_sin_id : m->w.rope_sin;     // qk_norm: as in enqueue_step
         q.nh = c.n_heads; q.nkv = c.n_kv_heads; q.qkv_bias = L.qkv_bias;
         KCHK(lk_mb_gemm(st, 2, q));
+        if (m->qk_norm)
+            KCHK(lk_qk_norm_rope(st, m->mb_qf, kf, nblk, c.n_heads, c.n_kv_heads, m->q_norm[l], m->k_norm[l], c.rms_eps, m->mb_pos, m->w.rope_cos, m->w.rope_sin));
         KCHK(lk_mb_tree_attn(st, m->mb_qf, m->kmain + (size_t)l * m->kv_layer_elems, m->vmain + (size_t)l * m->kv_layer_elems, kf, vf,
                              m->mb_rowmask, m->mb_meta, nblk, c.n_heads, c.n_kv_heads, c.max_keys, m->n_slots, mb_split(nblk, c.n_heads, c.balanced_wg[1] > 0 ? c.balanced_wg[1] : 256),
                              m->mb_opart, m->mb_mpart, m->mb_lpart, m->mb_attn_xp, c.sliding_window, c.kv_ring ? 1 : 0,

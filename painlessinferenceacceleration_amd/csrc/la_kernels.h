@@ -85,6 +85,9 @@ int lk_moe_accum(hipStream_t st, const float* slabs, int n_slabs, const float* r
 int lk_build_tree_inputs(hipStream_t st, const int* in, int* state, int* pos, uint64_t* rowmask, int* ids);
 int lk_qkv_post(hipStream_t st, const float* slabs, int n_slabs, int nh, int nkv, const int* pos, const void* rcos,
                 const void* rsin, void* qf, void* kfresh, void* vfresh, const void* qkv_bias = nullptr);
+// per-head q / k RMSNorm + RoPE in place on the QF / fresh KF fragments a QKV launch wrote with identity RoPE tables (la_qknorm.hip)
+int lk_qk_norm_rope(hipStream_t st, void* qf, void* kfresh, int nblk, int nh, int nkv, const void* q_weight, const void* k_weight,
+                    float eps, const int* pos, const void* rcos, const void* rsin);
 int lk_tree_attn(hipStream_t st, const void* qf, const void* kmain, const void* vmain, const void* kfresh,
                  const void* vfresh, const uint64_t* rowmask, const int* state, int nh, int nkv, int max_keys,
                  int nsplit, float* opart, float* mpart, float* lpart, void* attn_xp, int window = 0, int ring_keys = 0,

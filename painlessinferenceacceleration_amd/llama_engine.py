@@ -28,8 +28,11 @@ class LlamaShape(object):
 
     def __init__(self, n_layers=32, hidden=4096, n_heads=32, n_kv_heads=None, ffn=11008, vocab=32000,
                  rms_eps=1e-5, rope_theta=10000.0, head_dim=None, n_experts=0, top_k=2, norm_cast_first=False, sliding_window=0,
-                 qkv_bias=False):
+                 qkv_bias=False, qk_norm=False):
         self.n_layers, self.hidden, self.n_heads = n_layers, hidden, n_heads
+        # Qwen3: q_norm / k_norm, an RMSNorm over the head_dim features of every q and k head between the projection and RoPE
+        # (one device stage behind every QKV launch, csrc/la_qknorm.hip); the projections carry no bias
+        self.qk_norm = bool(qk_norm)
         # Qwen2 (Qwen1.5 / Qwen2 / Qwen2.5): q_proj / k_proj / v_proj carry a bias (qwen2/modeling_qwen2.py:234-237), added in the
         # fp32 epilogue of every QKV launch; o_proj and the MLP have none
         self.qkv_bias = bool(qkv_bias)
@@ -70,6 +73,16 @@ class LlamaShape(object):
         return cls(24, 896, 14, 2, 4864, 151936, 1e-6, rope_theta=1e6, norm_cast_first=True, qkv_bias=True)
 
     @classmethod
+    def qwen3_8b(cls):
+        """Qwen3-8B"""
+        return cls(36, 4096, 32, 8, 12288, 151936, 1e-6, rope_theta=1e6, head_dim=128, norm_cast_first=True, qk_norm=True)
+
+    @classmethod
+    def qwen3_0_6b(cls):
+        """Qwen3-0.6B: n_heads * head_dim = 2048 != hidden, tied embeddings (lm_head = embed_tokens)"""
+        return cls(28, 1024, 16, 8, 3072, 151936, 1e-6, rope_theta=1e6, head_dim=128, norm_cast_first=True, qk_norm=True)
+
+    @classmethod
     def from_hf(cls, cfg):
         """LlamaConfig / MistralConfig / MixtralConfig of transformers 4.3x (the reference's pins) or 5.x (rope_theta moved
         into cfg.rope_parameters)."""
@@ -81,18 +94,21 @@ class LlamaShape(object):
         if scaling and (scaling.get('rope_type', scaling.get('type', 'default')) not in ('default', None)):
             raise NotImplementedError(f'rope_scaling {scaling} is not supported by the RoPE tables of this path')
         head_dim = getattr(cfg, 'head_dim', None) or cfg.hidden_size // cfg.num_attention_heads
+        kind = getattr(cfg, 'model_type', 'llama')
+        if kind == 'qwen3' and getattr(cfg, 'attention_bias', False):
+            raise ValueError('qwen3 with attention_bias=True: the o_proj bias has no consumer here; refusing to drop it')
         return cls(cfg.num_hidden_layers, cfg.hidden_size, cfg.num_attention_heads,
                    getattr(cfg, 'num_key_value_heads', None), cfg.intermediate_size, cfg.vocab_size,
                    cfg.rms_norm_eps, float(rope_theta), head_dim=head_dim,
                    n_experts=getattr(cfg, 'num_local_experts', 0) or 0, top_k=getattr(cfg, 'num_experts_per_tok', 2),
-                   norm_cast_first=getattr(cfg, 'model_type', 'llama') in ('mistral', 'mixtral', 'qwen2'),
-                   qkv_bias=getattr(cfg, 'model_type', 'llama') == 'qwen2')
+                   norm_cast_first=kind in ('mistral', 'mixtral', 'qwen2', 'qwen3'),
+                   qkv_bias=kind == 'qwen2', qk_norm=kind == 'qwen3')
 
     def n_params_no_embed(self):
         hd = self.head_dim
         mlp = 3 * self.ffn * self.hidden * max(self.n_experts, 1) + self.n_experts * self.hidden
         per_layer = (self.n_heads + 2 * self.n_kv_heads) * hd * self.hidden + self.n_heads * hd * self.hidden \
-            + mlp + 2 * self.hidden + (self.n_heads + 2 * self.n_kv_heads) * hd * int(self.qkv_bias)
+            + mlp + 2 * self.hidden + (self.n_heads + 2 * self.n_kv_heads) * hd * int(self.qkv_bias) + 2 * hd * int(self.qk_norm)
         return self.n_layers * per_layer + self.hidden + self.vocab * self.hidden
 
 
@@ -199,6 +215,10 @@ def random_weights(shape, seed=0, std=0.02, device='cpu', dtype=torch.bfloat16, 
                     big = torch.rand(n, generator=g, device=device) < 0.1
                     b = torch.where(big, torch.randn(n, generator=g, device=device, dtype=torch.float32) * 4.0, b)
                 sd[p + f'self_attn.{nm}.bias'] = b.to(dtype)
+        if getattr(shape, 'qk_norm', False):
+            # away from 1, so that a lost or swapped norm weight changes the tokens
+            for nm in ('q_norm', 'k_norm'):
+                sd[p + f'self_attn.{nm}.weight'] = (0.2 + 2.0 * torch.rand(hd, generator=g, device=device, dtype=torch.float32)).to(dtype)
         if shape.n_experts > 0:                      # HF Mixtral naming (w1 = gate, w3 = up, w2 = down)
             sd[p + 'block_sparse_moe.gate.weight'] = w(shape.n_experts, shape.hidden)
             for e in range(shape.n_experts):
@@ -237,6 +257,30 @@ def check_biases(shape, state_dict):
         if k.endswith('.bias') and not (getattr(shape, 'qkv_bias', False) and qkv.search(k)):
             why = 'q/k/v biases need a shape with qkv_bias=True (Qwen2)' if qkv.search(k) else 'only q_proj / k_proj / v_proj biases are supported'
             raise ValueError(f'the state dict carries {k}: {why}; refusing to drop it')
+
+
+def check_qk_norm(shape, state_dict):
+    """q_norm / k_norm weights and shape.qk_norm (Qwen3) come together: a state dict that carries them under a shape without the stage
+    would run as a Llama and silently drop them, a shape with the stage needs every layer's pair.  Both are REFUSED."""
+    sd = state_dict or {}
+    norm = re.compile(r'\.self_attn\.[qk]_norm\.weight$')
+    have = [k for k in sd if norm.search(k)]
+    if not getattr(shape, 'qk_norm', False):
+        if have:
+            raise ValueError(f'the state dict carries {have[0]}: q/k norms need a shape with qk_norm=True (Qwen3); refusing to drop it')
+        return
+    if int(shape.head_dim) != 128:
+        raise ValueError(f'qk_norm with head_dim={shape.head_dim}: the q / k norm stage serves head_dim 128 only')
+    if getattr(shape, 'n_experts', 0) > 0:
+        raise ValueError('qk_norm: MoE models are not served with the q / k norm stage')
+    if sd:
+        for i in range(shape.n_layers):
+            for nm in ('q_norm', 'k_norm'):
+                k = f'model.layers.{i}.self_attn.{nm}.weight'
+                if k not in sd:
+                    raise ValueError(f'shape.qk_norm is set but the state dict has no {k}')
+                if sd[k].numel() != shape.head_dim:
+                    raise ValueError(f'{k}: {sd[k].numel()} values for head_dim {shape.head_dim}')
 
 
 PROJECTIONS = ('self_attn.q_proj', 'self_attn.k_proj', 'self_attn.v_proj', 'self_attn.o_proj', 'mlp.gate_proj', 'mlp.up_proj',
@@ -312,6 +356,9 @@ class LlamaVerifyEngine(object):
                  consume_state_dict=False, balanced=True, n_slots=1, fuse=0, max_blocks=0, kv_ring=False, dtype=None, lab=None,
                  weight_format=None):
         check_biases(shape, state_dict)
+        check_qk_norm(shape, state_dict)
+        if getattr(shape, 'qk_norm', False) and fuse:
+            raise ValueError('qk_norm: the fused norm / role-fused launches (fuse != 0) are not served with the q / k norm stage')
         # weight_format: None (the state dict decides) or 'fp8' — W8A16, see check_weight_format / quantize_fp8
         self.weight_format = check_weight_format(shape, state_dict, weight_format, gemm_cfg, fuse, max_blocks)
         w8 = self.weight_format == 'fp8'
@@ -399,6 +446,10 @@ class LlamaVerifyEngine(object):
                              'embed': self.embed.numel() * self.embed.element_size()}
         w.final_norm = packer.hold(src.take('model.norm.weight')).data_ptr()
         w.rope_cos, w.rope_sin = self.rope_cos.data_ptr(), self.rope_sin.data_ptr()
+        if getattr(shape, 'qk_norm', False):
+            # the QKV launches of a qk_norm model run with identity tables (cos = 1, sin = 0) and leave the rounded projection output;
+            # la_qk_norm_rope behind them normalises and applies the real tables
+            self.rope_cos_id, self.rope_sin_id = torch.ones_like(self.rope_cos), torch.zeros_like(self.rope_sin)
         w.layers = C.cast(layers, C.POINTER(_lib.LlamaLayerWeightsC))
         torch.cuda.synchronize(self.device)
 
@@ -428,7 +479,14 @@ class LlamaVerifyEngine(object):
         if nbytes <= 0:
             raise _lib.LookaheadHipError(f'la_llama_workspace_bytes: {_lib.last_error()}')
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self._h = self._lib.la_llama_create(C.byref(cfg), C.byref(w), self.workspace.data_ptr(), nbytes)
+        if getattr(shape, 'qk_norm', False):
+            qk = _lib.QkNormWeightsC()
+            self._qk_arrays = [(_lib.vp * shape.n_layers)(*[pair[i] for pair in packer.qk_norms]) for i in (0, 1)]
+            qk.q_norm, qk.k_norm = (C.cast(a, C.POINTER(_lib.vp)) for a in self._qk_arrays)
+            qk.rope_cos_id, qk.rope_sin_id = self.rope_cos_id.data_ptr(), self.rope_sin_id.data_ptr()
+            self._h = self._lib.la_llama_create_qk_norm(C.byref(cfg), C.byref(w), C.byref(qk), self.workspace.data_ptr(), nbytes)
+        else:
+            self._h = self._lib.la_llama_create(C.byref(cfg), C.byref(w), self.workspace.data_ptr(), nbytes)
         if not self._h:
             raise _lib.LookaheadHipError(f'la_llama_create: {_lib.last_error()}')
         self._alloc_host_blocks()

@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """Weight images — what LlamaVerifyEngine hands la_llama_create: every projection of a state dict repacked into MFMA-fragment order
 (la_pack_weight / la_pack_planned and their fp8 twins), plus the vectors that travel with them (fp8 row scales, the Qwen2 q/k/v
-bias, the norms).  Host side only: torch allocates and moves, the pack kernels live in liblookahead_hip.so.  WeightPacker is the one
+bias, the Qwen3 q/k norms, the norms).  Host side only: torch allocates and moves, the pack kernels live in liblookahead_hip.so.  WeightPacker is the one
 place that calls la_pack_* and la_rowplan; pack_layer turns one decoder layer into its LlamaLayerWeightsC."""
 import ctypes as C
 import os
@@ -97,6 +97,7 @@ class WeightPacker(object):
         self.sp = C.c_void_p(stream.cuda_stream)
         self.keep, self.nbytes = [], 0
         self.plans, self.plan_kinds = {}, {}
+        self.qk_norms = []          # (q_norm, k_norm) device pointers per layer of a Qwen3 model (pack_layer)
 
     def add_plan(self, slot, kind, n_rows, nwg):
         """la_rowplan deals the rows of a GEMM out to nwg workgroups: ask for the plan's size, then fill it.  -> False: the shape is
@@ -258,6 +259,10 @@ def pack_layer(packer, src, shape, i, L, lane_src, qkv_perm):
         wd, s_d = src.projection(p + 'mlp.down_proj')
         put('wdown', packer.plain(wd), s_d)
         del wd
+    if getattr(shape, 'qk_norm', False):
+        # not fields of L: la_llama_create_qk_norm takes them as one array per norm (LlamaVerifyEngine)
+        packer.qk_norms.append((packer.hold(src.take(p + 'self_attn.q_norm.weight')).data_ptr(),
+                                packer.hold(src.take(p + 'self_attn.k_norm.weight')).data_ptr()))
     L.norm1 = packer.hold(src.take(p + 'input_layernorm.weight')).data_ptr()
     L.norm2 = packer.hold(src.take(p + 'post_attention_layernorm.weight')).data_ptr()
     torch.cuda.synchronize(packer.device)
