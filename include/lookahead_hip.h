@@ -629,6 +629,34 @@ int la_llama_logprob_launches(la_llama* m);
 int la_llama_logprobs_read(la_llama* m, void* stream, int slot, int first_pos, int n, float* out);
 int la_logprob_rows(void* stream, const void* d_logits, int vocab, int n_rows, const int32_t* d_tok, float* d_out);
 
+/* ---- top-N log-probabilities on the device ----------------------------------------------------------------------------------------
+ * The alternatives of every token a step emits: for exactly the rows the stage above scores, the n tokens with the largest RAW
+ * logits of the row (as lm_head stored them: before any penalty, temperature or filter), each with its log-probability.
+ *   order   value descending, then token id ascending.  Values compare through the monotone 16-bit key of the sampling stage, so -0
+ *           and +0 are equal and a NaN logit is never listed; ties at the cut go to the lowest ids, so exactly n entries come out (a
+ *           row with fewer than n logits that are not NaN lists those, then pads with id -1 / NaN)
+ *   value   (x_v - m) - logf(float(Z * 2^-32)) with the m and the integer mass Z of the scalar stage: the entry of the chosen token
+ *           has the bits of the scalar value of that position; error against fp64 as stated for the scalar stage
+ *   exact   the selection is an exact radix select (two 256-bin levels over the key, then over the token id among the keys tied at
+ *           the cut) and one ranking of the n items: nothing depends on the order in which workgroups, waves or atomics arrive, so
+ *           the same logits row gives the same ids and the same bits on every run, at every row index and on every step form
+ * The log is int32 ids[n_slots][L][n] + float vals[n_slots][L][n], L = max(max_pos, max_keys) + 1 as above, written at pos + 1 like
+ * the scalar log (same LIMIT: a position outside stores nothing): n_slots * L * n * 8 bytes of device memory, allocated by the first
+ * la_llama_set_top_logprobs(n > 0) OUTSIDE the workspace (a model that never enables the stage allocates nothing) and freed by
+ * la_llama_destroy.  It is filled with 0xff bytes (id -1, value NaN) when the stage is switched on or n changes, and by la_llama_reset /
+ * la_llama_reset_slot while it is allocated.  The stage runs after the scalar stage whenever that one is on and n > 0, on every step
+ * form the scalar stage covers (mode 2 stores nothing; wide trees stay refused by the scalar stage's check); with n = 0 a step
+ * launches exactly what it launched before the stage existed.
+ *   la_llama_set_top_logprobs   n = 0 (the default): off; 1 <= n <= LA_TOPLP_MAX.  n > vocab or vocab % 8 != 0: LA_E_RANGE.
+ *                               Synchronises `stream`; a change of n drops the model's captured graphs.
+ *   la_llama_top_logprobs_read  synchronises `stream`, then ids / vals [n_pos][n] = the log of `slot` from first_pos on
+ *   la_top_logprob_rows         the row stage alone (unit parity), every row: logits [n_rows <= 64][vocab] of the library's 16-bit
+ *                               type -> d_ids / d_vals [n_rows][n] */
+#define LA_TOPLP_MAX 20
+int la_llama_set_top_logprobs(la_llama* m, void* stream, int n);
+int la_llama_top_logprobs_read(la_llama* m, void* stream, int slot, int first_pos, int n_pos, int32_t* ids, float* vals);
+int la_top_logprob_rows(void* stream, const void* d_logits, int vocab, int n_rows, int n, int32_t* d_ids, float* d_vals);
+
 /* ---- native decode loop: the per-step host work of lookahead_generation (pretrained_model.py:1172-1240) without the
  * interpreter: hier_get(last max_query_length tokens) -> la_llama_step -> stream_put, until max_length / eos / max_steps.
  * Greedy, empty logits-processor list (or the device repetition penalty: la_llama_set_repetition_penalty), decoding_mode

@@ -264,6 +264,9 @@ PROTOTYPES = {
     "la_llama_logprob_launches": (i32, vp),
     "la_llama_logprobs_read": (i32, vp, vp, i32, i32, i32, pf32),
     "la_logprob_rows": (i32, vp, vp, i32, i32, vp, vp),
+    "la_llama_set_top_logprobs": (i32, vp, vp, i32),
+    "la_llama_top_logprobs_read": (i32, vp, vp, i32, i32, i32, pi32, pf32),
+    "la_top_logprob_rows": (i32, vp, vp, i32, i32, i32, vp, vp),
 }
 
 # the kernel lab (include/lookahead_hip_lab.h): measurement knobs / A/B switches for scripts/ and the bitwise-identity tests — not part

@@ -17,7 +17,7 @@ build_one() {     # out.so, object dir, extra flags, extra sources
   for f in $SRCS; do
     local b="${f##*/}"; local o="$OBJ/${b%.*}.o"
     objs+=("$o")
-    if [ ! -f "$o" ] || [ "$HERE/$f" -nt "$o" ] || [ "$HERE/la_common.h" -nt "$o" ] || [ "$HERE/la_kernels.h" -nt "$o" ] || [ "$HERE/la_mblock.h" -nt "$o" ] || [ "$HERE/la_mb_forms.h" -nt "$o" ] || [ "$HERE/la_rows.h" -nt "$o" ] || [ "$HERE/la_epilogue.h" -nt "$o" ] || [ "$HERE/la_trie_dev.h" -nt "$o" ] || [ "$HERE/la_knobs.h" -nt "$o" ] || [ -n "$(find "$HERE/lab" -newer "$o" -name '*.inc' 2>/dev/null | head -1)" ] \
+    if [ ! -f "$o" ] || [ "$HERE/$f" -nt "$o" ] || [ "$HERE/la_common.h" -nt "$o" ] || [ "$HERE/la_kernels.h" -nt "$o" ] || [ "$HERE/la_mblock.h" -nt "$o" ] || [ "$HERE/la_mb_forms.h" -nt "$o" ] || [ "$HERE/la_rows.h" -nt "$o" ] || [ "$HERE/la_select.h" -nt "$o" ] || [ "$HERE/la_epilogue.h" -nt "$o" ] || [ "$HERE/la_trie_dev.h" -nt "$o" ] || [ "$HERE/la_knobs.h" -nt "$o" ] || [ -n "$(find "$HERE/lab" -newer "$o" -name '*.inc' 2>/dev/null | head -1)" ] \
        || [ "$HERE/../../include/lookahead_hip.h" -nt "$o" ] || [ "$HERE/../../include/lookahead_hip_lab.h" -nt "$o" ] || [ "$HERE/build.sh" -nt "$o" ]; then
       ( $HIPCC $FLAGS -x hip -c "$HERE/$f" -o "$o" ) &
       pids+=($!)

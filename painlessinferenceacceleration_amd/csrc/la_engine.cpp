@@ -129,6 +129,11 @@ struct la_llama {
     int lp_stride = 0;
     bool lp_on = false;
     int lp_launches = 0;
+    // top-N (la_llama_set_top_logprobs): ids / vals [n_slots][lp_stride][tlp_n], hipMalloc'ed by the first enable (outside the
+    // workspace), kept until destroy; tlp_cap = the n the allocation holds
+    int32_t* tlp_ids = nullptr;
+    float* tlp_vals = nullptr;
+    int tlp_n = 0, tlp_cap = 0;
     // per-head q / k RMSNorm stage (la_llama_create_qk_norm; la_qknorm.hip): the layers' norm weights and the identity RoPE tables the
     // QKV launches run with while it is on
     bool qk_norm = false;
@@ -368,8 +373,14 @@ extern "C" int64_t la_llama_workspace_bytes(const la_llama_config* cfg) {
 
 // the log-probability log of one slot (slot < 0: of every slot) := NaN (all-ones words)
 static hipError_t lp_clear(la_llama* m, hipStream_t st, int slot) {
-    if (slot < 0) return hipMemsetAsync(m->lp_log, 0xff, (size_t)m->n_slots * m->lp_stride * sizeof(float), st);
-    return hipMemsetAsync(m->lp_log + (size_t)slot * m->lp_stride, 0xff, (size_t)m->lp_stride * sizeof(float), st);
+    const size_t per = (size_t)m->lp_stride, n_all = slot < 0 ? (size_t)m->n_slots : 1, first = slot < 0 ? 0 : (size_t)slot;
+    if (m->tlp_ids && m->tlp_n > 0) {                      // the top-N log, in its current layout: id -1, value NaN
+        const size_t at = first * per * m->tlp_n, cnt = n_all * per * m->tlp_n;
+        hipError_t e = hipMemsetAsync(m->tlp_ids + at, 0xff, cnt * sizeof(int32_t), st);
+        if (e == hipSuccess) e = hipMemsetAsync(m->tlp_vals + at, 0xff, cnt * sizeof(float), st);
+        if (e != hipSuccess) return e;
+    }
+    return hipMemsetAsync(m->lp_log + first * per, 0xff, n_all * per * sizeof(float), st);
 }
 
 static la_llama* create(const la_llama_config* cfg, const la_llama_weights* w, const la_qk_norm_weights* qk, void* ws, int64_t ws_bytes) {
@@ -467,6 +478,8 @@ extern "C" void la_llama_destroy(la_llama* m) {
     if (m->pf_fork) (void)hipEventDestroy(m->pf_fork);
     if (m->pf_join) (void)hipEventDestroy(m->pf_join);
     if (m->pf_stream) (void)hipStreamDestroy(m->pf_stream);
+    if (m->tlp_ids) (void)hipFree(m->tlp_ids);
+    if (m->tlp_vals) (void)hipFree(m->tlp_vals);
     delete m;
 }
 
@@ -568,6 +581,11 @@ static int after_scan(la_llama* m, hipStream_t st, const StepRows& r) {
         LpArgs la{};
         la.p = pen_args(m, r, false); la.pos = r.pos; la.log = m->lp_log; la.stride = m->lp_stride;
         KCHK(lk_logprob_rows(st, la));
+        if (m->tlp_n > 0) {
+            TopLpArgs ta{};
+            ta.p = la.p; ta.pos = r.pos; ta.n = m->tlp_n; ta.log_ids = m->tlp_ids; ta.log_vals = m->tlp_vals; ta.stride = m->lp_stride;
+            KCHK(lk_top_logprob_rows(st, ta));
+        }
     }
     return LA_OK;
 }
@@ -1432,6 +1450,57 @@ extern "C" int la_logprob_rows(void* stream, const void* d_logits, int vocab, in
     la.p.kind = LA_PEN_ROWS; la.p.vocab = vocab; la.p.n_slots = 1; la.p.nblk = 1; la.p.n_rows = n_rows;
     la.p.logits = d_logits; la.p.out = (int*)d_tok; la.out = d_out;
     KCHK(lk_logprob_rows((hipStream_t)stream, la));
+    return LA_OK;
+}
+
+// ---- top-N log-probabilities on the device (la_logprob.hip: k_top_logprob_rows) ------------------------------------------------
+extern "C" int la_llama_set_top_logprobs(la_llama* m, void* stream, int n) {
+    if (!m) return LA_E_ARG;
+    if (n < 0 || n > LA_TOPLP_MAX) { la_set_error("top_logprobs: n must be 0 (off) .. LA_TOPLP_MAX (20)"); return LA_E_RANGE; }
+    if (n > 0 && ((m->cfg.vocab & 7) || n > m->cfg.vocab)) { la_set_error("top_logprobs: needs vocab % 8 == 0 and n <= vocab"); return LA_E_RANGE; }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipStreamSynchronize(st));                       // no step in flight runs a graph that is dropped below
+    if (n == m->tlp_n) return LA_OK;
+    drop_graphs(m);
+    if (n > m->tlp_cap) {
+        if (m->tlp_ids) (void)hipFree(m->tlp_ids);
+        if (m->tlp_vals) (void)hipFree(m->tlp_vals);
+        m->tlp_ids = nullptr; m->tlp_vals = nullptr; m->tlp_cap = 0; m->tlp_n = 0;
+        const size_t cnt = (size_t)m->n_slots * m->lp_stride * n;
+        HIPCHK(hipMalloc((void**)&m->tlp_ids, cnt * sizeof(int32_t)));
+        HIPCHK(hipMalloc((void**)&m->tlp_vals, cnt * sizeof(float)));
+        m->tlp_cap = n;
+    }
+    m->tlp_n = n;
+    if (n > 0) {                                            // a new layout: nothing of the old one is readable
+        const size_t cnt = (size_t)m->n_slots * m->lp_stride * n;
+        HIPCHK(hipMemsetAsync(m->tlp_ids, 0xff, cnt * sizeof(int32_t), st));
+        HIPCHK(hipMemsetAsync(m->tlp_vals, 0xff, cnt * sizeof(float), st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return LA_OK;
+}
+
+extern "C" int la_llama_top_logprobs_read(la_llama* m, void* stream, int slot, int first_pos, int n_pos, int32_t* ids, float* vals) {
+    if (!m || slot < 0 || slot >= m->n_slots || first_pos < 0 || n_pos < 0 || (n_pos > 0 && (!ids || !vals)) || (int64_t)first_pos + n_pos > m->lp_stride) return LA_E_ARG;
+    if (m->tlp_n <= 0) { la_set_error("top_logprobs_read: the stage is off (la_llama_set_top_logprobs(n > 0))"); return LA_E_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t at = ((size_t)slot * m->lp_stride + first_pos) * m->tlp_n, cnt = (size_t)n_pos * m->tlp_n;
+    if (cnt > 0) {
+        HIPCHK(hipMemcpyAsync(ids, m->tlp_ids + at, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(vals, m->tlp_vals + at, cnt * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return LA_OK;
+}
+
+extern "C" int la_top_logprob_rows(void* stream, const void* d_logits, int vocab, int n_rows, int n, int32_t* d_ids, float* d_vals) {
+    if (!d_logits || !d_ids || !d_vals || n_rows < 1 || n_rows > LA_TREE_MAX) return LA_E_ARG;
+    if (vocab <= 0 || (vocab & 7) || n < 1 || n > LA_TOPLP_MAX || n > vocab) { la_set_error("top_logprob_rows: needs vocab % 8 == 0 and 1 <= n <= min(LA_TOPLP_MAX, vocab)"); return LA_E_RANGE; }
+    TopLpArgs ta{};
+    ta.p.kind = LA_PEN_ROWS; ta.p.vocab = vocab; ta.p.n_slots = 1; ta.p.nblk = 1; ta.p.n_rows = n_rows;
+    ta.p.logits = d_logits; ta.n = n; ta.out_ids = d_ids; ta.out_vals = d_vals;
+    KCHK(lk_top_logprob_rows((hipStream_t)stream, ta));
     return LA_OK;
 }
 

@@ -208,3 +208,17 @@ struct LpArgs {
     float* out;
 };
 int lk_logprob_rows(hipStream_t st, const LpArgs& a);
+
+// ... and the top-N list of the same rows (k_top_logprob_rows): ids / vals [n] at log[slot][pos[row] + 1], or at out[row] (unit entry)
+#ifndef LA_TOPLP_MAX
+#define LA_TOPLP_MAX 20
+#endif
+struct TopLpArgs {
+    PenArgs p;                        // as LpArgs::p (p.out is not read)
+    const int* pos;
+    int n;                            // 1 .. LA_TOPLP_MAX, <= vocab
+    int* log_ids; float* log_vals;    // [n_slots][stride][n], or null (unit entry): out_ids / out_vals [rows][n]
+    int stride;
+    int* out_ids; float* out_vals;
+};
+int lk_top_logprob_rows(hipStream_t st, const TopLpArgs& a);

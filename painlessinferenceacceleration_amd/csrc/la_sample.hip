@@ -29,22 +29,10 @@
 #include "la_kernels.h"
 #include "la_mblock.h"
 #include "la_rows.h"
+#include "la_select.h"
 
 #define SAMP_THREADS 1024
-#define SAMP_COPIES 8
 typedef unsigned long long u64;
-
-// storage bits -> monotone key (0 = NaN: never kept); key -> value
-__device__ __forceinline__ unsigned samp_key(bf16_t b) {
-    unsigned u = b;
-    const unsigned mag = u & 0x7fffu;
-    if (mag > (LA_DTYPE == 1 ? 0x7c00u : 0x7f80u)) return 0u;
-    if (mag == 0u) u = 0u;
-    return (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
-}
-__device__ __forceinline__ float samp_val(unsigned key) {
-    return bf2f((bf16_t)((key & 0x8000u) ? (key & 0x7fffu) : (~key & 0xffffu)));
-}
 
 // Philox4x32-10 (Salmon et al., SC'11)
 __host__ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
@@ -56,11 +44,6 @@ __host__ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1,
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ u64 shfl_up64(u64 v, int o) {
-    const unsigned lo = __shfl_up((unsigned)v, o, 64), hi = __shfl_up((unsigned)(v >> 32), o, 64);
-    return ((u64)hi << 32) | lo;
 }
 
 // the keys of every 16-byte chunk of the row, penalty applied: f(chunk index, keys[8]); four chunks per thread and round in flight
@@ -89,44 +72,6 @@ __device__ __forceinline__ void samp_scan(const bf16_t* __restrict__ lg, int nch
             f(c, keys);
         }
     }
-}
-
-// Wave 0, after the 8 copies of a 256-bin histogram are complete: the HIGHEST bin b whose suffix sum S(b) = sum_{j >= b} h[j] reaches the
-// target, and the sum above it.  frac < 0: the target is `target`; else target = max(1, floor(frac * total)) and *s_target receives it.
-// sel[0] = bin or -1 (the target is never reached), sel64[0] = S(b + 1), sel64[1] = the target used.
-__device__ __forceinline__ void samp_select(const u64* hist, bool as_u32, u64 target, double frac, int* sel, u64* sel64) {
-    const int lane = (int)threadIdx.x;                 // < 64
-    u64 h[4], loc = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int b = 255 - 4 * lane - j;
-        u64 s = 0;
-        if (as_u32) { for (int c = 0; c < SAMP_COPIES; ++c) s += ((const unsigned*)hist)[b * SAMP_COPIES + c]; }
-        else { for (int c = 0; c < SAMP_COPIES; ++c) s += hist[b * SAMP_COPIES + c]; }
-        h[j] = s; loc += s;
-    }
-    u64 inc = loc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = shfl_up64(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (frac >= 0.0) {
-        const unsigned tlo = __shfl((unsigned)inc, 63, 64), thi = __shfl((unsigned)(inc >> 32), 63, 64);
-        const u64 total = ((u64)thi << 32) | tlo;
-        target = (u64)(frac * (double)total);
-        if (target < 1) target = 1;
-    }
-    u64 run = inc - loc, above = 0;
-    int hit = -1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (hit < 0 && run + h[j] >= target) { hit = 255 - 4 * lane - j; above = run; }
-        run += h[j];
-    }
-    const unsigned long long bal = __ballot(hit >= 0);
-    if (bal == 0ull) { if (lane == 0) { sel[0] = -1; sel64[0] = 0; sel64[1] = target; } }
-    else if (lane == __builtin_ctzll(bal)) { sel[0] = hit; sel64[0] = above; sel64[1] = target; }
 }
 
 __global__ __launch_bounds__(SAMP_THREADS) void k_sample_rows(const SampArgs a) {

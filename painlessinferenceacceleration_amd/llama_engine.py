@@ -496,6 +496,7 @@ class LlamaVerifyEngine(object):
         self._pen_ctx = {}
         self.sampling = False
         self.logprobs_on = False
+        self.top_logprobs_n = 0
         self.reset()
 
     def _alloc_host_blocks(self):
@@ -602,6 +603,25 @@ class LlamaVerifyEngine(object):
         check(self._lib.la_llama_logprobs_read(self._h, self._sp(), int(slot), int(first_pos), int(n), out.ctypes.data_as(_lib.pf32)),
               'logprobs_read')
         return out
+
+    def set_top_logprobs(self, n):
+        """The top-N list of the log-probability stage: n = 0 (the default) off, 1 .. 20 = for every token a step emits while
+        set_logprobs(True), the n tokens with the largest raw logits (value descending, then id ascending) with their
+        log-probabilities, kept in a position-indexed log per slot next to the scalar one; read it with top_logprobs().  The log is
+        allocated by the first call with n > 0; switching n drops the captured graphs."""
+        check(self._lib.la_llama_set_top_logprobs(self._h, self._sp(), int(n)), 'set_top_logprobs')
+        self.top_logprobs_n = int(n)
+
+    def top_logprobs(self, slot, first_pos, n_pos):
+        """-> (ids int32 [n_pos][n], vals float32 [n_pos][n]): the top-N log of `slot` from position first_pos on (positions are
+        indices in the unpadded sequence, as logprobs(); (-1, NaN): nothing emitted there)"""
+        n = getattr(self, 'top_logprobs_n', 0)
+        assert n > 0, 'top_logprobs: the stage is off (set_top_logprobs(n))'
+        ids = np.empty((int(n_pos), n), dtype=np.int32)
+        vals = np.empty((int(n_pos), n), dtype=np.float32)
+        check(self._lib.la_llama_top_logprobs_read(self._h, self._sp(), int(slot), int(first_pos), int(n_pos),
+                                                   ids.ctypes.data_as(_lib.pi32), vals.ctypes.data_as(_lib.pf32)), 'top_logprobs_read')
+        return ids, vals
 
     def logprob_launches(self):
         """steps launched with the log-probability stage since the engine was created"""

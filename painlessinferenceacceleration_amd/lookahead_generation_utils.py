@@ -175,16 +175,41 @@ def plan_logprobs(requested, engine, host_walk, do_sample=False, seed=None, enab
     return True
 
 
+TOP_LOGPROBS_MAX = 20        # LA_TOPLP_MAX (include/lookahead_hip.h)
+
+
+def plan_top_logprobs(requested, engine):
+    """decoding_kwargs['top_logprobs'] / top_logprobs=n: how many alternatives per generated token the device step lists
+    (LlamaVerifyEngine.set_top_logprobs: csrc/la_logprob.hip).  -> 0 when not requested, else n (1 .. 20); ValueError otherwise.  A
+    request with n > 0 implies output_logprobs: hand `requested or n > 0` to plan_logprobs, which refuses the host-walk paths."""
+    if requested is None or requested is False or (not isinstance(requested, bool) and requested == 0):
+        return 0
+    if isinstance(requested, bool) or not isinstance(requested, int) or not 1 <= requested <= TOP_LOGPROBS_MAX:
+        raise ValueError(f'top_logprobs: an int 1 .. {TOP_LOGPROBS_MAX} (got {requested!r})')
+    if not hasattr(engine, 'set_top_logprobs'):
+        raise ValueError('top_logprobs: this engine has no top-N log-probability stage')
+    return int(requested)
+
+
+def read_top_logprobs(engine, slot, first_pos, n_pos):
+    """the top-N log of one slot as the front doors return it: per position a list of n (token_id, logprob) pairs, most likely first"""
+    ids, vals = engine.top_logprobs(slot, first_pos, n_pos)
+    return [[(int(t), float(v)) for t, v in zip(ids[p], vals[p])] for p in range(n_pos)]
+
+
 @contextmanager
-def device_stages(engine, plan, slots, logprobs=False):
+def device_stages(engine, plan, slots, logprobs=False, top_logprobs=0):
     """The stages of `plan` (plan_device_stages; None: nothing) switched on for one request and off again, also after an exception:
     the next request starts without them.  slots: (slot, sampling stream word, token row the slot's penalty context is seeded
     with) per sequence — the batch loops seed with the padded row (what the reference's walk hands the processor); row None: the
-    prefill seeds the context with the prompt itself.  logprobs (plan_logprobs): the log-probability stage, likewise."""
+    prefill seeds the context with the prompt itself.  logprobs (plan_logprobs): the log-probability stage, likewise; top_logprobs
+    (plan_top_logprobs, only with logprobs): its top-N list, switched off before the scalar stage."""
     penalty, sampling = (None, None) if plan is None else (plan['penalty'], plan['sampling'])
     try:
         if logprobs:
             engine.set_logprobs(True)
+            if top_logprobs:
+                engine.set_top_logprobs(top_logprobs)
         if penalty is not None:
             engine.set_repetition_penalty(penalty)
             for slot, _, row in slots:
@@ -201,7 +226,11 @@ def device_stages(engine, plan, slots, logprobs=False):
         if sampling is not None:
             engine.set_sampling(False)
         if logprobs:
-            engine.set_logprobs(False)
+            try:
+                if top_logprobs:
+                    engine.set_top_logprobs(0)
+            finally:
+                engine.set_logprobs(False)
 
 
 def pick_token(logits_processor, do_sample, ctx_ids, logits_row, device):
@@ -495,8 +524,11 @@ def run_generate(model, batch, inputs, generation_config, logits_processor, stop
                               else getattr(model.generation_config, 'eos_token_id', None),
                               logits_processor=procs if len(procs) else None, do_sample=ga.do_sample,
                               stopping_criteria=ga.stopping_criteria, device_processors=dk.get('device_processors', True),
-                              sample_seed=dk.get('sample_seed', None), output_logprobs=bool(dk.get('output_logprobs', False)), **extra)
+                              sample_seed=dk.get('sample_seed', None), output_logprobs=bool(dk.get('output_logprobs', False)), **extra,
+                              **({'top_logprobs': dk['top_logprobs']} if dk.get('top_logprobs', 0) else {}))
     out_kwargs = {}
-    if dk.get('output_logprobs', False):          # the plain leg's (sequences, logprobs)
+    if dk.get('top_logprobs', 0):                 # the plain leg's (sequences, logprobs, top_logprobs)
+        out, out_kwargs['logprobs'], out_kwargs['top_logprobs'] = out
+    elif dk.get('output_logprobs', False):        # the plain leg's (sequences, logprobs)
         out, out_kwargs['logprobs'] = out
     return LookaheadDecoderOnlyOutput(sequences=out, kwargs=out_kwargs) if ga.return_dict_in_generate else out

@@ -16,6 +16,7 @@ import torch
 from . import _lib
 from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, _custom_stop, _max_length_of, _parents_of,  # noqa: F401
                                           begin_request, device_stages, gc_paused, pick_token, plan_device_stages, plan_logprobs,
+                                          plan_top_logprobs, read_top_logprobs,
                                           run_generate)
 
 _ONE = np.array([1], dtype=np.uint64)
@@ -166,13 +167,15 @@ class LookaheadPreTrainedModel(object):
             sequential = False
         # decoding_kwargs['output_logprobs']: the log-probability stage of the device step (csrc/la_logprob.hip) — honoured whenever
         # the request runs the device accept, refused (before any engine or trie call) when it would take the host walk
-        want_logprobs = plan_logprobs(decoding_kwargs.get('output_logprobs', False), eng, sequential,
+        # decoding_kwargs['top_logprobs'] = n: + the n most likely tokens of every generated position (implies output_logprobs)
+        top_n = plan_top_logprobs(decoding_kwargs.get('top_logprobs', 0), eng)
+        want_logprobs = plan_logprobs(decoding_kwargs.get('output_logprobs', False) or top_n > 0, eng, sequential,
                                       do_sample=do_sample, seed=decoding_kwargs.get('sample_seed', None),
                                       enabled=decoding_kwargs.get('device_processors', True),
                                       scores=scores is not None or bool(decoding_kwargs.get('fresh_scores', False)), wide=wide,
                                       device_trie=bool(decoding_kwargs.get('device_trie', False)),
                                       gather=decoding_kwargs.get('gather', None) is not None)
-        logprobs = None
+        logprobs = top_logprobs = None
         cap = eng._capacity() if hasattr(eng, '_capacity') else eng.max_keys
         assert stop_max_length + decoding_length + 1 <= cap, f'engine KV capacity {cap} < max_length + decoding_length + 1'
         # Sharded job (distributed.py): decoding_kwargs['gather'] = AcceptedTokenGather(..., b_loc=1, mode='strict' | 'split-phase').
@@ -223,7 +226,7 @@ class LookaheadPreTrainedModel(object):
         last_scores = None         # what the reference's model_kwargs['next_tokens_scores'] holds
         flushed = False
         try:
-            with device_stages(eng, stages, [(0, 0, None)], logprobs=want_logprobs):      # (row None: prefill seeds the penalty context with the prompt)
+            with device_stages(eng, stages, [(0, 0, None)], logprobs=want_logprobs, **({'top_logprobs': top_n} if top_n else {})):      # (row None: prefill seeds the penalty context with the prompt)
                 while True:
                     if first:
                         host_row = sequential or scores is not None      # the last prompt row's logits must stay readable
@@ -334,6 +337,8 @@ class LookaheadPreTrainedModel(object):
                         break
                 if want_logprobs:          # read once: the steps kept the position-indexed log current on the device
                     logprobs = [float(x) for x in eng.logprobs(0, n_prompt, len(seq) - n_prompt)]
+                    if top_n:
+                        top_logprobs = read_top_logprobs(eng, 0, n_prompt, len(seq) - n_prompt)
         finally:
             # an exception mid-generation must not leave this request's stream buffer / input frequencies behind (they would
             # mix into the next request); the reference flushes on the normal path only (pretrained_model.py:1236-1239)
@@ -352,6 +357,8 @@ class LookaheadPreTrainedModel(object):
             kwargs = {k: decoding_kwargs[k] for k in ('dls', 'edls', 'fts', 'qts')}
             if want_logprobs:
                 kwargs['logprobs'] = logprobs
+            if top_n:
+                kwargs['top_logprobs'] = top_logprobs
             if scores is not None:
                 scores = tuple(s_.to(out_device) for s_ in scores)
             return LookaheadDecoderOnlyOutput(sequences=sequences, scores=scores, attentions=None, hidden_states=None,
@@ -361,7 +368,7 @@ class LookaheadPreTrainedModel(object):
     # ---------------------------------------------------------------------------------- plain greedy (mode off)
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, eos_token_id=None, logits_processor=None, do_sample=False,
-                      stopping_criteria=None, device_processors=True, sample_seed=None, output_logprobs=False):
+                      stopping_criteria=None, device_processors=True, sample_seed=None, output_logprobs=False, top_logprobs=0):
         """Plain decoding through the same engine (T=1 blocks): the `use_lookahead=False` leg of the reference's
         examples (examples/llama_example.py:39-69).  With a processor list or sampling each token is picked on the host
         from the block's logits row (forward-only step + commit) — except a list that is exactly one repetition penalty, or a
@@ -369,7 +376,8 @@ class LookaheadPreTrainedModel(object):
         lookahead_generation uses (device_processors=False: the host pick).  With the same seed this is the no-draft comparator of
         the sampling lookahead loop: token for token the same sequence.  output_logprobs=True: -> (sequences, list of one
         log-probability per generated token) from the device stage lookahead_generation uses — its no-draft comparator; a request
-        that would pick on the host is refused (ValueError)."""
+        that would pick on the host is refused (ValueError).  top_logprobs=n (implies output_logprobs): -> (sequences, logprobs, per
+        generated token a list of the n most likely (token_id, logprob) pairs) from the top-N stage."""
         eos = set([eos_token_id] if isinstance(eos_token_id, int) else (eos_token_id or []))
         seq = input_ids[0].tolist()
         n_prompt = len(seq)
@@ -378,14 +386,15 @@ class LookaheadPreTrainedModel(object):
         stages = plan_device_stages(logits_processor, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
         if stages is not None:
             host_pick = False
-        want_logprobs = plan_logprobs(output_logprobs, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
+        top_n = plan_top_logprobs(top_logprobs, eng)
+        want_logprobs = plan_logprobs(output_logprobs or top_n > 0, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
         eng.reset()
         custom_stop = _custom_stop(stopping_criteria)        # the caller's criteria besides the length bound, once per token
 
         def pick(row):
             return pick_token(logits_processor, do_sample, seq, eng.logits()[row], eng.device)[0]
 
-        with device_stages(eng, stages, [(0, 0, None)], logprobs=want_logprobs):
+        with device_stages(eng, stages, [(0, 0, None)], logprobs=want_logprobs, **({'top_logprobs': top_n} if top_n else {})):
             tok = eng.prefill(seq, fast=False) if host_pick else eng.prefill(seq)
             if host_pick:
                 tok = pick((len(seq) - 1) % 64)
@@ -401,7 +410,11 @@ class LookaheadPreTrainedModel(object):
                 seq.append(tok)
             if want_logprobs:
                 logprobs = [float(x) for x in eng.logprobs(0, n_prompt, len(seq) - n_prompt)]
+            if top_n:
+                tops = read_top_logprobs(eng, 0, n_prompt, len(seq) - n_prompt)
         sequences = torch.tensor([seq], dtype=torch.long, device=input_ids.device)
+        if top_n:
+            return sequences, logprobs, tops
         return (sequences, logprobs) if want_logprobs else sequences
 
     # ------------------------------------------------------------------------------------------- front door

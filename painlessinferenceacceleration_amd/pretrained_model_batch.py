@@ -21,7 +21,8 @@ import torch
 
 from . import _lib
 from .lookahead_generation_utils import (LookaheadDecoderOnlyOutput, _custom_stop, _parents_of, begin_request, device_stages,
-                                          gc_paused, pick_token, plan_device_stages, plan_logprobs, run_generate)
+                                          gc_paused, pick_token, plan_device_stages, plan_logprobs, plan_top_logprobs,
+                                          read_top_logprobs, run_generate)
 
 _ONE = np.array([1], dtype=np.uint64)
 
@@ -183,14 +184,16 @@ class LookaheadPreTrainedModel(object):
             decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the penalty / sampling stage)
         # decoding_kwargs['output_logprobs']: the log-probability stage of the device step (csrc/la_logprob.hip) — honoured whenever
         # the request runs the device accept, refused (before any engine or trie call) when it would take the host walk
-        want_logprobs = plan_logprobs(decoding_kwargs.get('output_logprobs', False), eng, sequential, do_sample=do_sample,
+        # decoding_kwargs['top_logprobs'] = n: + the n most likely tokens of every generated position (implies output_logprobs)
+        top_n = plan_top_logprobs(decoding_kwargs.get('top_logprobs', 0), eng)
+        want_logprobs = plan_logprobs(decoding_kwargs.get('output_logprobs', False) or top_n > 0, eng, sequential, do_sample=do_sample,
                                       seed=decoding_kwargs.get('sample_seed', None), enabled=decoding_kwargs.get('device_processors', True),
                                       scores=scores is not None or bool(decoding_kwargs.get('fresh_scores', False)),
                                       wide=min(int(decoding_length), _cap_rows) > _lib.LA_TREE_MAX,
                                       device_trie=bool(decoding_kwargs.get('device_trie', False)), gather=gather is not None)
         if want_logprobs:
             decoding_kwargs['device_trie'] = False        # (no auto-chained device trie under the stage)
-        logprobs = None
+        logprobs = top_logprobs = None
         gi = (lambda b_: gather.global_index(b_)) if gather is not None else (lambda b_: b_)
         # decoding_kwargs['overlap_trie_update'] (extension, off by default: the reference updates before it queries): the trie update
         # of step k runs on the host AFTER the verify pass of step k + 1 has been queued — drafts see a step's tokens one step later
@@ -217,7 +220,8 @@ class LookaheadPreTrainedModel(object):
         try:
             ts = time.time()
             eng.reset_slot(-1)
-            with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)], logprobs=want_logprobs):      # (stream word = batch index, seed = padded row)
+            with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)], logprobs=want_logprobs,
+                               **({'top_logprobs': top_n} if top_n else {})):      # (stream word = batch index, seed = padded row)
                 # prefill: valid prompt tokens of every sample, packed into shared 64-row chain blocks
                 prompts = {i: ids0[i][am[i] == 1].tolist() for i in range(bs)}
                 multi = bool(getattr(eng, 'max_blocks', 0))
@@ -436,6 +440,8 @@ class LookaheadPreTrainedModel(object):
                 if want_logprobs:
                     # read once: slot i's log is indexed by the position in the UNPADDED sequence; each list is cut at its own stop
                     logprobs = [[float(x) for x in eng.logprobs(i, len(prompts[i]), len(finished_rows[i]) - P)] for i in range(bs)]
+                    if top_n:
+                        top_logprobs = [read_top_logprobs(eng, i, len(prompts[i]), len(finished_rows[i]) - P) for i in range(bs)]
         except BaseException:
             # A failure (or an interrupt) mid-request must not leave the trie with this request's stream buffers / input frequencies, and in a
             # sharded job must not strand the other ranks: they are (or will be) waiting in the per-step collective.  The failing rank keeps
@@ -462,6 +468,8 @@ class LookaheadPreTrainedModel(object):
             kwargs = {k: decoding_kwargs[k] for k in ('dls', 'edls', 'fts', 'qts')}
             if want_logprobs:
                 kwargs['logprobs'] = logprobs
+            if top_n:
+                kwargs['top_logprobs'] = top_logprobs
             return LookaheadDecoderOnlyOutput(sequences=sequences, scores=scores, attentions=None, hidden_states=None,
                                               kwargs=kwargs)
         return sequences
@@ -491,13 +499,15 @@ class LookaheadPreTrainedModel(object):
     @torch.no_grad()
     def greedy_search(self, input_ids, max_length, attention_mask=None, eos_token_id=None, pad_token_id=0,
                       logits_processor=None, do_sample=False, stopping_criteria=None, device_processors=True,
-                      sample_seed=None, output_logprobs=False):
+                      sample_seed=None, output_logprobs=False, top_logprobs=0):
         """Plain decoding of the whole batch through the same engine (one row per sample per block).  With a processor list or
         sampling every token is picked on the host from the sample's logits row (forward-only step + la_llama_bcommit).
         `stopping_criteria`: the caller's criteria besides the length bound (MaxTimeCriteria, custom ones) are evaluated per
         row after every token, on the row's own tokens — a row they stop is retired like one that met eos.
         output_logprobs=True: -> (sequences, one list per sample of one log-probability per generated token) from the device stage
-        lookahead_generation uses — its no-draft comparator; a request that would pick on the host is refused (ValueError)."""
+        lookahead_generation uses — its no-draft comparator; a request that would pick on the host is refused (ValueError).
+        top_logprobs=n (implies output_logprobs): -> (sequences, logprobs, one list per sample of, per generated token, the n most
+        likely (token_id, logprob) pairs) from the top-N stage."""
         ids0 = input_ids.cpu().numpy().astype(np.int64)
         bs, P = ids0.shape
         am = np.ones_like(ids0) if attention_mask is None else attention_mask.cpu().numpy().astype(np.int64)
@@ -511,11 +521,16 @@ class LookaheadPreTrainedModel(object):
         stages = plan_device_stages(logits_processor, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
         if stages is not None:
             host_pick = False
-        want_logprobs = plan_logprobs(output_logprobs, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
+        top_n = plan_top_logprobs(top_logprobs, eng)
+        want_logprobs = plan_logprobs(output_logprobs or top_n > 0, eng, host_pick, do_sample=do_sample, seed=sample_seed, enabled=device_processors)
         eng.reset_slot(-1)
-        with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)], logprobs=want_logprobs):
+        with device_stages(eng, stages, [(i, i, ids0[i].tolist()) for i in range(bs)], logprobs=want_logprobs,
+                           **({'top_logprobs': top_n} if top_n else {})):
             sequences, n_new = self._greedy_search(eng, ids0, prompts, host_pick, multi, logits_processor, do_sample, stopping_criteria,
                                                    max_length, eos, pad_token_id, input_ids.device)
+            if top_n:
+                return (sequences, [[float(x) for x in eng.logprobs(i, len(prompts[i]), n_new[i])] for i in range(bs)],
+                        [read_top_logprobs(eng, i, len(prompts[i]), n_new[i]) for i in range(bs)])
             if want_logprobs:
                 return sequences, [[float(x) for x in eng.logprobs(i, len(prompts[i]), n_new[i])] for i in range(bs)]
             return sequences
